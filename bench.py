@@ -6,13 +6,16 @@ anchor matching, MobileNet-v2 + refine heads forward, smooth-L1 loss, backward, 
 at 720x1280, batch 8 per GPU (configs[1] on one GPU; configs[2] = batch 64 on 8 GPUs is
 the same per-GPU work, weak scaling).  Every kernel is librod (HIP, gfx950).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   N>1: launched by torch.distributed.run, one rank per GPU, RCCL all-reduce of the flat
   gradient buffer (sum, global-batch normalisation), clip after reduce.
 
-Prints one JSON line (rank 0) with roofline (live HIP-event timing of the dominant
-kernel over the timed region) and cpu_baseline (the oracle — a PyTorch-CPU restatement
-of the same step — on a bounded sample, rank 0 at N=1 only).
+Prints one JSON line (rank 0): the headline figure and ms_per_step of the K timed steps.
+A plain run does nothing else.  --full adds roofline (live HIP-event timing of the dominant
+kernel), the per-kernel and whole-step rooflines, the TFRecord, fp32, data-parallel-overhead
+and inference legs, and cpu_baseline (the oracle — a PyTorch-CPU restatement of the same
+step — on a bounded sample, rank 0 at N=1 only).  --dump-outputs DIR writes what the last
+timed step computed (losses, updated parameters, gradients, BatchNorm statistics) as .npy.
 """
 import argparse
 import json
@@ -83,7 +86,42 @@ def parse():
                     help='N=1: feed the step from a TFRecord of synthetic 1280x720 JPEG frames through the '
                          'host JPEG decode + GPU augmentation (train.py input path) and report it under "tfrecord"')
     ap.add_argument('--no-tfrecord-leg', dest='tfrecord_leg', action='store_false')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true', default=False,
+                    help='also run everything beside the headline figure: the "roofline" probe steps, "kernels" / '
+                         '"step_roofline", the TFRecord, fp32, data-parallel-overhead and inference legs, the CPU '
+                         'baselines, --probe-table (each still has its own --no-... switch).  Without it the run '
+                         'sets up, warms up, times --steps steps and prints the result line')
+    ap.add_argument('--dump-outputs', dest='dump_outputs', default=None, metavar='DIR',
+                    help='after the timed steps write what the last timed step returned and left behind (rank 0: '
+                         'its losses, the parameters after its SGD update, its gradients, the BatchNorm moving '
+                         'statistics) as DIR/<name>.npy, float32')
+    args = ap.parse_args()
+    if not args.full:
+        args.cpu_baseline = args.inference = args.inference_1080 = False
+        args.fp32_leg = args.tfrecord_leg = args.dp_leg = False
+        args.kernel_steps, args.probe, args.probe_table = 0, '', None
+    return args
+
+
+DUMP_MAX_BYTES = 60 << 20   # of array data; with the .npy headers still under 64 MB
+
+
+def dump_outputs(path, losses, store):
+    """The last timed step as its caller sees it: the losses it returned and the state it left
+    in the parameter store.  At most DUMP_MAX_BYTES in all: the arrays are written smallest
+    first, and one over an even share of what is left is cut to a fixed, seeded sample of its
+    elements (in index order)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {'losses': torch.stack([l.detach().float().reshape(()) for l in losses]),
+              'params': store.flat, 'grads': store.flat_grad, 'bn_buffers': store.flat_buf}
+    left = DUMP_MAX_BYTES // 4
+    for i, (name, t) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].numel())):
+        a = t.detach().float().reshape(-1).cpu().numpy()
+        share = left // (len(arrays) - i)
+        left -= min(a.size, share)
+        if a.size > share:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def cpu_baseline(H, W):
@@ -511,10 +549,12 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:   # before anything below runs further steps on this trainer
+        dump_outputs(args.dump_outputs, losses, tr.net.store)
 
     table, design = _abi.PROBE.table(), _abi.PROBE.design_table()
     probe_steps = args.steps
-    if use_graph:
+    if use_graph and probe_set:
         # a replayed graph makes no host calls to time: the dominant kernel's rooflines come
         # from two eager steps after the timed region (same kernels, same arguments)
         _abi.PROBE.arm(probe_set)
@@ -639,8 +679,9 @@ def main():
                            'batchnorm': 'sync (global batch)' if args.sync_bn else 'per rank'} if world > 1 else {}),
                        **({} if args.train_range == 'REFINE' else {'fix_refine': args.fix_refine})},
             'loss': round(loss_val, 5), 'loss_first_step': round(first_loss, 5) if first_loss is not None else None,
-            'roofline': rl,
         }
+        if probe_set:   # nothing was probed without --full (or with --probe ''): no roofline to report
+            out['roofline'] = rl
         if step_rl is not None:
             out['step_roofline'] = step_rl
         if kernels is not None:

@@ -16,9 +16,11 @@ mocks).  Usage:  python tests/golden/make_golden.py
 """
 import importlib.abc
 import importlib.machinery
+import io
 import json
 import os
 import sys
+import zipfile
 from unittest import mock
 
 import numpy as np
@@ -80,7 +82,13 @@ def capture_geometry(nt, anc, H, W):
         assert len(muls) == 2 and len(adds) == 2
         arrs['center_%d' % l] = np.stack([adds[0], adds[1], muls[0], muls[1]], -1)   # (cy, cx, h, w)
     tf.while_loop.side_effect = None
-    np.savez_compressed(os.path.join(OUT, 'ref_anchor_geom_%dx%d.npz' % (H, W)), **arrs)
+    # an .npz with LZMA members (np.load reads it as any other): the regular anchor grids pack
+    # 15-20x tighter than with deflate, which keeps the 720p / 1080p fixtures far below 1 MiB
+    with zipfile.ZipFile(os.path.join(OUT, 'ref_anchor_geom_%dx%d.npz' % (H, W)), 'w', zipfile.ZIP_LZMA) as z:
+        for k, a in arrs.items():
+            buf = io.BytesIO()
+            np.save(buf, a)
+            z.writestr(k + '.npy', buf.getvalue())
 
 
 def main():

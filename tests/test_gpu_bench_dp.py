@@ -51,7 +51,7 @@ def test_bench_two_ranks_inference_replicas(dev):
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
            '--master-addr', '127.0.0.1', '--master-port', str(_port()), os.path.join(ROOT, 'bench.py'),
            '--gpus', '2', '--steps', '1', '--warmup', '1', '--height', '160', '--width', '288', '--batch', '2',
-           '--no-cpu-baseline', '--no-inference-1080', '--kernel-steps', '0']
+           '--full', '--no-cpu-baseline', '--no-inference-1080', '--kernel-steps', '0']
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=200)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]

@@ -86,12 +86,12 @@ for step in "$@"; do
     streamtest) run streamtest 300 python -u -m pytest tests/test_gpu_pwproj.py tests/test_gpu_kernels.py -k "pw_stream or pw_proj or prologue" -m gpu -v --timeout=200 --timeout-method thread -p no:cacheprovider ;;
     projtest) run projtest 300 python -u -m pytest tests/test_gpu_pwproj.py -m gpu -v --timeout=200 --timeout-method thread -p no:cacheprovider ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python bench.py --steps 10 --warmup 3 ;;
-    benchfast) run benchfast 400 python bench.py --steps 5 --warmup 2 --no-cpu-baseline ;;
-    benchfp32) run benchfp32 600 python bench.py --dtype fp32 --steps 5 --warmup 2 --no-cpu-baseline --no-inference ;;
-    benchgred) run benchgred 400 env ROD_ENABLE=gred python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-inference --kernel-steps 0 &&
-               run benchbase 400 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-inference --kernel-steps 0 &&
-               run benchgreddw 400 env ROD_ENABLE=gred,dwbn python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-inference --kernel-steps 0 ;;
+    bench) run bench 600 python bench.py --full --steps 10 --warmup 3 ;;
+    benchfast) run benchfast 400 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline ;;
+    benchfp32) run benchfp32 600 python bench.py --full --dtype fp32 --steps 5 --warmup 2 --no-cpu-baseline --no-inference ;;
+    benchgred) run benchgred 400 env ROD_ENABLE=gred python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-inference --kernel-steps 0 &&
+               run benchbase 400 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-inference --kernel-steps 0 &&
+               run benchgreddw 400 env ROD_ENABLE=gred,dwbn python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-inference --kernel-steps 0 ;;
     hosttime) run hosttime 300 python tools/host_time.py --steps 10 ;;
     hostprof) run hostprof 300 python -m cProfile -s tottime tools/host_time.py --steps 5 ;;
     bnu) run bnu4 300 python tools/bn_bench.py --out /tmp/${TAG}_bn4.pt && run bnu8 300 env ROD_BN_RED_U=8 python tools/bn_bench.py --check /tmp/${TAG}_bn4.pt ;;
@@ -114,18 +114,18 @@ for step in "$@"; do
             run bw1 300 env ROD_BN_RED_WANT=2048 python tools/bn_bench.py --check /tmp/${TAG}_bn.pt &&
             run bw2 300 env ROD_BN_RED_WANT=512 python tools/bn_bench.py --check /tmp/${TAG}_bn.pt &&
             run bw3 300 env ROD_BN_RED_WANT=256 python tools/bn_bench.py --check /tmp/${TAG}_bn.pt ;;
-    benchall) run benchall 600 python bench.py --steps 5 --warmup 2 --train_range ALL --no-cpu-baseline --no-inference ;;
-    benchallfr) run benchallfr 600 python bench.py --steps 5 --warmup 2 --train_range ALL --no-fix-refine --no-cpu-baseline --no-inference ;;
-    benchaug) run benchaug 600 python bench.py --steps 10 --warmup 3 --augment --no-cpu-baseline --no-inference --probe-table $OUT/${TAG}_probe_aug.json ;;
-    benchaug2) run benchaug2 600 python bench.py --steps 10 --warmup 3 --augment --no-cpu-baseline --no-inference ;;
+    benchall) run benchall 600 python bench.py --full --steps 5 --warmup 2 --train_range ALL --no-cpu-baseline --no-inference ;;
+    benchallfr) run benchallfr 600 python bench.py --full --steps 5 --warmup 2 --train_range ALL --no-fix-refine --no-cpu-baseline --no-inference ;;
+    benchaug) run benchaug 600 python bench.py --full --steps 10 --warmup 3 --augment --no-cpu-baseline --no-inference --probe-table $OUT/${TAG}_probe_aug.json ;;
+    benchaug2) run benchaug2 600 python bench.py --full --steps 10 --warmup 3 --augment --no-cpu-baseline --no-inference ;;
     cli) run cli_train 300 python road-object-detection-for-bdd100k_amd/train.py --train_range=ALL --batch_size=2 --max_number_of_steps=4 --log_every_n_steps=2 --save_every_n_steps=4 --checkpoint_refine=None --train_dir=gpurun_out/ckpt --summary_dir=gpurun_out/summ &&
          run cli_eval 300 python road-object-detection-for-bdd100k_amd/evaluate.py --checkpoint_path=gpurun_out/ckpt --batch_size=2 --num_images=6 --eval_dir=gpurun_out/eval &&
          run cli_predict 300 python road-object-detection-for-bdd100k_amd/predict.py --checkpoint_all=gpurun_out/ckpt/mobilenet_v2.model --batch_size=2 --num_batches=2 --output=gpurun_out/pred.json ;;
-    probetable) run probetable 400 python bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --probe-table $OUT/${TAG}_probe_table.json ;;
-    probetableall) run probetableall 400 python bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-inference --train_range ALL --probe-table $OUT/${TAG}_probe_table_all.json ;;
-    prof) run prof 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o run --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --kernel-steps 0 &&
+    probetable) run probetable 400 python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --probe-table $OUT/${TAG}_probe_table.json ;;
+    probetableall) run probetableall 400 python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-inference --train_range ALL --probe-table $OUT/${TAG}_probe_table_all.json ;;
+    prof) run prof 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o run --output-format csv -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --kernel-steps 0 &&
          summ $OUT/prof_$TAG normalize_image 5+2 "REFINE train step bf16 b8 720p, graph replays" ;;
-    profall) run profall 600 rocprofv3 --kernel-trace --stats -d $OUT/profall_$TAG -o run --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-inference --train_range ALL ;;
+    profall) run profall 600 rocprofv3 --kernel-trace --stats -d $OUT/profall_$TAG -o run --output-format csv -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-inference --train_range ALL ;;
     profpred) run profpred 400 rocprofv3 --kernel-trace --stats -d $OUT/profpred_$TAG -o run --output-format csv -- python3 tools/predict_bench.py --res 720 --batch 32 --iters 10 &&
          summ $OUT/profpred_$TAG normalize_image 10 "predict path bf16 b32 720p, graph replays" ;;
     profpred1080) run profpred1080 400 rocprofv3 --kernel-trace --stats -d $OUT/profpred1080_$TAG -o run --output-format csv -- python3 tools/predict_bench.py --res 1080 --batch 8 --iters 10 &&
