@@ -20,13 +20,52 @@ from . import _abi
 from ._abi import ROD_ACT_LEAKY, ROD_ACT_NONE, ROD_ACT_RELU, ROD_ACT_RELU6  # noqa: F401
 
 _DT = {torch.float32: _abi.ROD_F32, torch.bfloat16: _abi.ROD_BF16}
-# debug bisection switches (comma list): splitk, epistats, convstats, dwstats, bnpro, pwgred, stembn, pro3
-_DISABLE = set(os.environ.get("ROD_DISABLE", "").split(","))
-# opt-in paths (comma list): gred = BatchNorm-backward reduction fused into the backward-data
-# epilogues (measured slower than the separate streaming reduce on MI355X: DESIGN.md §6);
-# gredpw = the same for the 1x1 convs that take the streaming kernel (measured neutral); dwbn,
-# side: DESIGN.md §6
-_ENABLE = set(os.environ.get("ROD_ENABLE", "").split(","))
+
+
+def _switches(value, known):
+    """The comma list `value` of an environment switch variable as a set.  A token that is not
+    in `known` (a misspelling, or a path that has been retired) raises: it would otherwise be
+    ignored and the run would silently measure the defaults."""
+    got = {t.strip() for t in value.split(",")} - {""}
+    for t in sorted(got - set(known)):
+        raise ValueError("unknown switch %r (known: %s)" % (t, ", ".join(known)))
+    return got
+
+
+# ROD_DISABLE: bisection / A-B switches, each turns one default path off.  Every token the code
+# reads is listed here (rod.ops and nets/); tests and tools also add / discard them in place.
+_DISABLE_KNOWN = (
+    "bnpro",      # BatchNorm-apply load prologues: every Pending is materialised (nets/)
+    "chainpro",   # the block 1 -> block 2 project output kept Pending (nets/backbone/mobilenet_v2.py)
+    "pro3",       # large 3x3 convs write act(BN(x)) once instead of applying it per tap
+    "cinpad",     # inference: zero-padding of the heads' last 3x3 convs to Cin % 8 == 0
+    "bnepi",      # inference: rod_conv_fwd_bnact (BatchNorm + act in the conv epilogue)
+    "splitk",     # the split-K workspace of rod_conv_fwd
+    "prepcache",  # the per-store cache of GEMM-layout weights (_prep)
+    "epistats",   # BatchNorm statistics from the producer's epilogue parts
+    "convstats",  # ... for conv2d(want_stats=True)
+    "dwstats",    # ... for dw3x3(want_stats=True)
+    "pwbwd",      # rod_pw_bwd, the fused expand backward
+    "pwgred",     # rod_pw_bwd_gred*, the fused project backward with the input BatchNorm's sums
+    "dwpw",       # rod_dw3x3_bwd_fused_pw (the depthwise-output gradient left unmaterialised)
+    "dwfused",    # rod_dw3x3_bwd_fused*: the unfused depthwise backward chain
+    "dwfused2",   # ... at stride 2 only
+    "bnbwd",      # rod_conv_bwd_data_bn
+    "stembn",     # rod_stem_wgrad_bn
+    "slabdefer",  # the batched weight-gradient slab sums (SlabDefer)
+    "rc",         # every recompute form of the expand output (ABI 23)
+    "nostore",    # leaving a stride-2 block's expand output unwritten
+    "rcinf",      # inference: the recompute chain in preference to the fused block
+    "rcinf1",     # ... at stride 1 only
+    "irblock",    # inference: rod_ir_block_fwd
+)
+# ROD_ENABLE: opt-in paths, off by default (measured not faster: DESIGN.md §6).
+_ENABLE_KNOWN = (
+    "rcdw",         # the depthwise forward recomputes a stored expand output (dw_rc_ok)
+    "irblock_all",  # inference: the fused block wherever it is supported (tools/irblock_bench.py)
+)
+_DISABLE = _switches(os.environ.get("ROD_DISABLE", ""), _DISABLE_KNOWN)
+_ENABLE = _switches(os.environ.get("ROD_ENABLE", ""), _ENABLE_KNOWN)
 
 
 def dtcode(t: torch.Tensor) -> int:
@@ -42,53 +81,6 @@ def stream() -> int:
 
 def workspace(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
-
-
-class _Side:
-    """Weight gradients on a side stream (single process): a conv's / depthwise's filter
-    gradient only reads (x, dy) and writes its own slot of the flat gradient buffer, so it can
-    run beside the backward-data chain that the rest of the backward waits on.  The side stream
-    forks from the main stream where dy is ready and is joined once, before the optimizer step
-    (join()); the tensors it reads stay referenced until then, so the caching allocator cannot
-    hand their memory to main-stream work in between.  Works under HIP-graph capture (the fork /
-    join become graph edges).  Opt-in (ROD_ENABLE=side: measured slower, the overlapped kernels
-    contend for the same CUs and HBM — DESIGN.md §6); never under data parallelism (the gradient
-    buckets are reduced from inside backward); outside SIDE.backward (tests, other callers of
-    .backward()) everything stays on the calling stream."""
-
-    def __init__(self):
-        self.on = False
-        self.stream = None
-        self.keep = []
-
-    def backward(self, loss, device):
-        """graph.backward(loss) with the weight gradients on the side stream, joined before
-        returning (so every caller after it sees complete gradients on the main stream)."""
-        from . import graph
-        if "side" in _DISABLE:
-            return graph.backward(loss)
-        if self.stream is None or self.stream.device != torch.device(device):
-            self.stream = torch.cuda.Stream(device=device)
-        self.on = True
-        try:
-            graph.backward(loss)
-        finally:
-            self.on = False
-            torch.cuda.current_stream().wait_stream(self.stream)
-            self.keep.clear()
-
-    def run(self, fn, *keep):
-        if not self.on:
-            return fn()
-        self.stream.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(self.stream):
-            r = fn()
-        self.keep.extend(keep)
-        return r
-
-
-
-SIDE = _Side()
 
 
 class LevelStreams:
@@ -204,6 +196,22 @@ def _mark_written(p):
     cb = getattr(p, "_rod_on_grad", None)
     if cb is not None:
         cb(p)
+
+
+def _bn_grad_slots(gamma, beta, need_g, need_b):
+    """(dgamma, dbeta) destinations of a BatchNorm backward: the flat-buffer slots where needed."""
+    return (grad_slot(gamma) if need_g else None), (grad_slot(beta) if need_b else None)
+
+
+def _bn_grads_written(gamma, beta, need_g, need_b):
+    if need_g:
+        _mark_written(gamma)
+    if need_b:
+        _mark_written(beta)
+
+
+def _det(t):
+    return None if t is None else t.detach()
 
 
 def same_pad(size: int, stride: int, k: int = 3):
@@ -345,26 +353,25 @@ def _bn_backward(dz, y, mean, rstd, gamma, beta, act, need_g, need_b):
     M = N * H * W
     dz = dz.contiguous()
     dy = torch.empty_like(y)
-    dg = grad_slot(gamma) if need_g else None
-    db = grad_slot(beta) if need_b else None
+    dg, db = _bn_grad_slots(gamma, beta, need_g, need_b)
     if db is None:
         db = torch.empty(C, dtype=torch.float32, device=y.device)  # the kernel always may write dbeta
     ws = workspace(_abi.query("rod_bn_bwd_workspace", M, C), y.device)
     _abi.call("rod_bn_bwd", dz, y, mean, rstd, gamma, beta, dy, dg, db, ws, M, C, 0, 0, 0, act, dtcode(y),
               stream())
-    if need_g:
-        _mark_written(gamma)
-    if need_b:
-        _mark_written(beta)
+    _bn_grads_written(gamma, beta, need_g, need_b)
     return dy
 
 
-# BatchNorm-backward sums handed from a consumer's backward to the producer's: the fused
-# depthwise backward (rod_dw3x3_bwd_fused) computes, beside the gradient dx it returns
-# for its input act(BN(y)), that BatchNorm's backward sums over (dx, y).  The producer node
-# (_ConvBN) receives exactly that dx as its dz when the depthwise is the only consumer, and then
-# finalizes the sums instead of running rod_bn_bwd_reduce over (dz, y).  Entries hold their dx
-# (so its memory cannot be reused while listed) and are dropped when the backward ends.
+# BatchNorm-backward sums handed from a consumer's backward to the producer's.  Two families of
+# kernels produce them: the fused depthwise backwards (rod_dw3x3_bwd_fused / _fused_pw /
+# _fused_rc, in _DWBN.backward) and the fused project / 16 -> 96 expand backwards
+# (rod_pw_bwd_gred / _gred_dyp / _gred_rc, in _ConvBN.backward).  Each computes, beside the
+# gradient dx it returns for its input act(BN(y)), that BatchNorm's backward sums over (dx, y).
+# The producer node (_ConvBN after a depthwise, _DWBN or the previous block's _ConvBN after a
+# 1x1 conv) receives exactly that dx as its dz when the kernel's node is the only consumer, and
+# then finalizes the sums instead of running rod_bn_bwd_reduce over (dz, y).  Entries hold their
+# dx (so its memory cannot be reused while listed) and are dropped when the backward ends.
 # An entry is accepted only for the very tensor it was made for, or a view of the same storage
 # whose version counter is unchanged: a gradient summed IN PLACE into dx (a second consumer of
 # the depthwise input) shares dx's pointer and shape but bumps its version, and then the
@@ -441,8 +448,7 @@ def bn_bwd_coef_from_parts(parts, M, C, rstd, gamma, beta, need_g, need_b):
     coef [3, C]; dgamma / dbeta to the parameters' slots.  Under SyncBatchNorm the parts are
     all-gathered first (the parameter gradients stay this rank's own sums, as bn_bwd_reduce)."""
     coef = torch.empty(3 * C, dtype=torch.float32, device=parts.device)
-    dg = grad_slot(gamma) if need_g else None
-    db = grad_slot(beta) if need_b else None
+    dg, db = _bn_grad_slots(gamma, beta, need_g, need_b)
     nparts = parts.shape[0]
     if SYNC_BN is not None:
         if dg is not None or db is not None:
@@ -453,10 +459,7 @@ def bn_bwd_coef_from_parts(parts, M, C, rstd, gamma, beta, need_g, need_b):
                   stream())
     else:
         _abi.call("rod_bn_bwd_finalize", parts, nparts, M, C, rstd, gamma, dg, db, coef, stream())
-    if need_g:
-        _mark_written(gamma)
-    if need_b:
-        _mark_written(beta)
+    _bn_grads_written(gamma, beta, need_g, need_b)
     return coef
 
 
@@ -466,8 +469,7 @@ def bn_bwd_reduce(dz, y, mean, rstd, gamma, beta, act, need_g, need_b):
     C = y.shape[-1]
     M = y.numel() // C
     coef = torch.empty(3 * C, dtype=torch.float32, device=y.device)
-    dg = grad_slot(gamma) if need_g else None
-    db = grad_slot(beta) if need_b else None
+    dg, db = _bn_grad_slots(gamma, beta, need_g, need_b)
     if SYNC_BN is not None:
         dz = dz.contiguous()
         nparts = _sync_nparts(M)
@@ -484,10 +486,7 @@ def bn_bwd_reduce(dz, y, mean, rstd, gamma, beta, act, need_g, need_b):
         ws = workspace(_abi.query("rod_bn_bwd_workspace", M, C), y.device)
         _abi.call("rod_bn_bwd_reduce", dz, y, mean, rstd, gamma, beta, dg, db, coef, ws, M, C, act, dtcode(y),
                   stream())
-    if need_g:
-        _mark_written(gamma)
-    if need_b:
-        _mark_written(beta)
+    _bn_grads_written(gamma, beta, need_g, need_b)
     return coef
 
 
@@ -515,10 +514,10 @@ def pw_bwd(dz, y, mean, rstd, gamma, beta, act, coef, x, xpro, wt1, want_dx, dw,
 def pw_bwd_rc_ok(M, Cin, Cout, dtype):
     """The expand backward recomputes its pre-BatchNorm y from x (ABI 23, rod_pw_bwd_rc /
     rod_pw_bwd_gred_rc) instead of reading it: ROD_DISABLE=rc turns it off (A/B).  Taken for
-    block 1's 16 -> 96 (720p b8: 683 -> 549 us); the 24 -> 144 form measured slower (266 -> 310 us
-    a call: one wave per SIMD, nothing hides the recompute's LDS round trip) and is opt-in
-    (ROD_ENABLE=rc144)."""
-    if "rc" in _DISABLE or dtype != torch.bfloat16 or (Cin != 16 and "rc144" not in _ENABLE):
+    block 1's 16 -> 96 only (720p b8: 683 -> 549 us); the 24 -> 144 form measured slower (266 -> 310
+    us a call: one wave per SIMD, nothing hides the recompute's LDS round trip), so it runs only
+    where the expand output is not stored (_nostore_ok, which asks the library directly)."""
+    if "rc" in _DISABLE or dtype != torch.bfloat16 or Cin != 16:
         return False
     return bool(_abi.lib().rod_pw_bwd_rc_supported(int(M), int(Cin), int(Cout), _DT[dtype]))
 
@@ -629,24 +628,6 @@ def dw_pw_ok(src_dw, x, Cout, ipro):
                                                          dtcode(x)))
 
 
-def _bn_backward_parts(dz, y, mean, rstd, gamma, beta, act, parts, need_g, need_b):
-    """Finish a BatchNorm backward whose reduction the producer of dz already did in its
-    epilogue (gred partial sums): rod_bn_bwd_finalize -> rod_bn_bwd_apply."""
-    N, H, W, C = y.shape
-    M = N * H * W
-    coef = torch.empty(3 * C, dtype=torch.float32, device=y.device)
-    dg = grad_slot(gamma) if need_g else None
-    db = grad_slot(beta) if need_b else None
-    _abi.call("rod_bn_bwd_finalize", parts, parts.shape[0], M, C, rstd, gamma, dg, db, coef, stream())
-    dy = torch.empty_like(y)
-    _abi.call("rod_bn_bwd_apply", dz, y, mean, rstd, gamma, beta, coef, dy, M, C, act, dtcode(y), stream())
-    if need_g:
-        _mark_written(gamma)
-    if need_b:
-        _mark_written(beta)
-    return dy
-
-
 def _gred_args(g):
     """The seven gred arguments (pre-BatchNorm y, mean, rstd, gamma, beta, act, parts)."""
     if g is None:
@@ -659,8 +640,7 @@ def _split_in(x):
     An owned Pending's gamma / beta are passed detached: its producer writes their gradients."""
     if isinstance(x, Pending):
         if x.owned:
-            det = lambda t: None if t is None else t.detach()
-            return x.y, det(x.gamma), det(x.beta), x.mean, x.rstd, x.act, x.training, True
+            return x.y, _det(x.gamma), _det(x.beta), x.mean, x.rstd, x.act, x.training, True
         return x.y, x.gamma, x.beta, x.mean, x.rstd, x.act, x.training, False
     return x, None, None, None, None, 0, False, False
 
@@ -703,12 +683,7 @@ class _DW3x3(torch.autograd.Function):
             if ctx.pro and not ctx.training:
                 raise RuntimeError("BatchNorm backward in inference mode is not part of the reference graph")
             dx = torch.empty_like(x)   # gradient wrt the dw input (the BatchNorm output when pro)
-            gred = None
-            if ctx.pro and "gred" in _ENABLE and not ctx.owned and SYNC_BN is None:   # sums in the epilogue
-                nparts = _abi.lib().rod_dw3x3_bwd_data_gred_parts(N, H, W, C, s, dtcode(x))
-                parts = torch.empty((nparts, 2, C), dtype=torch.float32, device=x.device)
-                gred = (x, mean, rstd, gamma, beta, ctx.act, parts)
-            _abi.call("rod_dw3x3_bwd_data", dy, w, dx, *_gred_args(gred), N, H, W, C, s, pt, pl, Ho, Wo, dtcode(x),
+            _abi.call("rod_dw3x3_bwd_data", dy, w, dx, *_gred_args(None), N, H, W, C, s, pt, pl, Ho, Wo, dtcode(x),
                       stream())
         if ctx.needs_input_grad[1]:
             g = grad_slot(w)
@@ -717,10 +692,7 @@ class _DW3x3(torch.autograd.Function):
                       dtcode(x), stream())
             _mark_written(w)
         if ctx.pro and dx is not None and not ctx.owned:
-            if gred is not None:
-                dx = _bn_backward_parts(dx, x, mean, rstd, gamma, beta, ctx.act, gred[6], need_g, need_b)
-            else:
-                dx = _bn_backward(dx, x, mean, rstd, gamma, beta, ctx.act, need_g, need_b)
+            dx = _bn_backward(dx, x, mean, rstd, gamma, beta, ctx.act, need_g, need_b)
         return dx, None, None, None, None, None, None, None, None, None, None
 
 
@@ -746,10 +718,17 @@ def _prep(w, mode, dtype, Cout, Cin, ks):
     return wt
 
 
-def conv_fwd_raw(x, wt, b, y, N, H, W, Cin, Cout, ksize, stat_parts=None, pro=None, gred=None):
-    """rod_conv_fwd with its split-K workspace (allocated only when the plan splits)."""
+def _splitk_ws(device, N, H, W, Cin, Cout, ksize):
+    """The split-K workspace of rod_conv_fwd and its kin: allocated only when the plan splits
+    (None otherwise, or with ROD_DISABLE=splitk: the entry then does not split)."""
     nb = 0 if "splitk" in _DISABLE else _abi.query("rod_conv_fwd_workspace", N, H, W, Cin, Cout, ksize)
-    ws = workspace(nb, x.device) if nb else None
+    return workspace(nb, device) if nb else None
+
+
+def conv_fwd_raw(x, wt, b, y, N, H, W, Cin, Cout, ksize, stat_parts=None, pro=None, gred=None):
+    """rod_conv_fwd with its split-K workspace.  gred: the seven ABI-4 arguments (_gred_args) —
+    no path in this package passes them; tests/test_gpu_gred.py does."""
+    ws = _splitk_ws(x.device, N, H, W, Cin, Cout, ksize)
     _abi.call("rod_conv_fwd", x, *_pro_args(pro), wt, b, y, ws, stat_parts, *_gred_args(gred), N, H, W, Cin, Cout,
               ksize, 0, 0, dtcode(x), stream())
 
@@ -793,11 +772,7 @@ class _Conv(torch.autograd.Function):
                 raise RuntimeError("BatchNorm backward in inference mode is not part of the reference graph")
             wt1 = _prep(w, 1, x.dtype, Cout, Cin, ks)
             dx = torch.empty_like(x)   # gradient wrt the conv input (the BatchNorm output when pro)
-            gred = None
-            if ctx.pro and "gred" in _ENABLE and not ctx.owned and SYNC_BN is None:   # sums in the epilogue
-                parts = torch.empty((-(-(N * H * W) // 128), 2, Cin), dtype=torch.float32, device=x.device)
-                gred = (x, mean, rstd, gamma, beta, ctx.act, parts)
-            conv_fwd_raw(dy, wt1, None, dx, N, H, W, Cout, Cin, ks, gred=gred)
+            conv_fwd_raw(dy, wt1, None, dx, N, H, W, Cout, Cin, ks)
         need_w = ctx.needs_input_grad[1]
         need_bias = b is not None and ctx.needs_input_grad[2]
         if need_w or need_bias:
@@ -813,10 +788,7 @@ class _Conv(torch.autograd.Function):
             if need_bias:
                 _mark_written(b)
         if ctx.pro and dx is not None and not ctx.owned:
-            if gred is not None:
-                dx = _bn_backward_parts(dx, x, mean, rstd, gamma, beta, ctx.act, gred[6], need_g, need_b)
-            else:
-                dx = _bn_backward(dx, x, mean, rstd, gamma, beta, ctx.act, need_g, need_b)
+            dx = _bn_backward(dx, x, mean, rstd, gamma, beta, ctx.act, need_g, need_b)
         return dx, None, None, None, None, None, None, None, None, None, None, None
 
 
@@ -904,8 +876,7 @@ def materialize(p, residual=None):
     if not isinstance(p, Pending):
         return p
     if p.owned:
-        det = lambda t: None if t is None else t.detach()
-        return _BNApplyOwned.apply(p.y, residual, p.mean, p.rstd, det(p.gamma), det(p.beta), p.act)
+        return _BNApplyOwned.apply(p.y, residual, p.mean, p.rstd, _det(p.gamma), _det(p.beta), p.act)
     return _BNAct.apply(p.y, p.gamma, p.beta, residual, p.mean, p.rstd, p.act, p.training)
 
 
@@ -934,6 +905,15 @@ def _needs(p):
     return p is not None and p.requires_grad
 
 
+def _bn_bwd_coef(parts, dz, y, mean, rstd, gamma, beta, act):
+    """coef [3, C] of an owned BatchNorm's backward (dgamma / dbeta to their slots): finalized
+    from the sums a consumer's backward handed over (parts), else reduced over (dz, y)."""
+    C = y.shape[-1]
+    if parts is not None:
+        return bn_bwd_coef_from_parts(parts, y.numel() // C, C, rstd, gamma, beta, _needs(gamma), _needs(beta))
+    return bn_bwd_reduce(dz, y, mean, rstd, gamma, beta, act, _needs(gamma), _needs(beta))
+
+
 def bn_bwd_dy(dz, y, mean, rstd, gamma, beta, act, need_g, need_b):
     """d/dy of act(BN(y)) from dz, dgamma / dbeta into their slots.  Small tensors (<= 4096
     rows: the deep maps and the heads' last levels) take rod_bn_bwd, which runs the reduction,
@@ -953,10 +933,9 @@ def _pw_fused_ok(M, Cin, Cout, dtype):
     return M >= 200_000 and Cout >= 2 * Cin and pw_bwd_supported(Cin, Cout, dtype)
 
 
-def _bwd_data_bn_ok(M, Cout, Cin, dtype, ipro):
-    # the opt-in gred form of the backward-data (ROD_ENABLE=gredpw, below) keeps the two-launch
-    # chain, and so do the shapes whose plain backward-data takes the K <= 96 streaming kernel
-    return "bnbwd" not in _DISABLE and not (ipro is not None and "gredpw" in _ENABLE) and \
+def _bwd_data_bn_ok(M, Cout, Cin, dtype):
+    # the shapes whose plain backward-data takes the K <= 96 streaming kernel keep the two-launch chain
+    return "bnbwd" not in _DISABLE and \
         bool(_abi.lib().rod_conv_bwd_data_bn_supported(int(Cout), int(Cin), _DT[dtype])) and \
         not _abi.lib().rod_conv_fwd_stream_ok(int(M), int(Cout), int(Cin), _DT[dtype])
 
@@ -971,28 +950,23 @@ def conv_bwd_data_bn(dz, y, mean, rstd, gamma, beta, act, coef, w):
     wt1 = _prep(w, 1, y.dtype, Cout, Cin, 1)
     dy = torch.empty_like(y)
     dx = torch.empty((N, H, W_, Cin), dtype=y.dtype, device=y.device)
-    nb = 0 if "splitk" in _DISABLE else _abi.query("rod_conv_fwd_workspace", 1, 1, M, Cout, Cin, 1)
-    ws = workspace(nb, y.device) if nb else None
+    ws = _splitk_ws(y.device, 1, 1, M, Cout, Cin, 1)
     _abi.call("rod_conv_bwd_data_bn", dz.contiguous(), y, mean, rstd, gamma, beta, act, coef, wt1, dy, dx, ws, M,
               Cout, Cin, dtcode(y), stream())
     return dy, dx
 
 
 def _conv_bwd_from_dy(x, w, b, ks, dy, pro, need_dx):
-    """rod_conv_fwd (mode-1 weights) for dx and rod_conv_wgrad for dw / db from a dense dy
-    (the weight gradient on the side stream when SIDE is on)."""
+    """rod_conv_wgrad for dw / db and rod_conv_fwd (mode-1 weights) for dx from a dense dy."""
     N, H, W, Cin = x.shape
     Cout = w.shape[0]
     need_w, need_bias = _needs(w), _needs(b)
     if need_w or need_bias:
         gw = grad_slot(w) if need_w else torch.empty(w.shape, dtype=torch.float32, device=x.device)
         gb = grad_slot(b) if need_bias else None
-
-        def wgrad():
-            ws = workspace(_abi.query("rod_conv_wgrad_workspace", N, H, W, Cin, Cout, ks), x.device)
-            _abi.call("rod_conv_wgrad", x, *_pro_args(pro), dy, gw, gb, ws, N, H, W, Cin, Cout, ks, 0, 0,
-                      dtcode(x), stream())
-        SIDE.run(wgrad, x, dy, gw, pro)
+        ws = workspace(_abi.query("rod_conv_wgrad_workspace", N, H, W, Cin, Cout, ks), x.device)
+        _abi.call("rod_conv_wgrad", x, *_pro_args(pro), dy, gw, gb, ws, N, H, W, Cin, Cout, ks, 0, 0,
+                  dtcode(x), stream())
         if need_w:
             _mark_written(w)
         if need_bias:
@@ -1001,21 +975,7 @@ def _conv_bwd_from_dy(x, w, b, ks, dy, pro, need_dx):
     if need_dx:
         wt1 = _prep(w, 1, x.dtype, Cout, Cin, ks)
         dx = torch.empty_like(x)
-        gred = None
-        if pro is not None and ks == 1 and "gredpw" in _ENABLE and \
-                _abi.lib().rod_conv_fwd_stream_ok(N * H * W, Cout, Cin, dtcode(x)):
-            # opt-in (ROD_ENABLE=gredpw): dx is the gradient of the input's BatchNorm output (an
-            # owned Pending: the depthwise BatchNorm of the block, conv_blocks.py:238-247); the
-            # streaming backward-data also forms that BatchNorm's backward sums over (dx, x),
-            # handed to its producer (_DWBN), which then skips its rod_bn_bwd_reduce pass.
-            # Correct (tests/test_gpu_gred.py, the step tests) but measured no faster: the
-            # reduce passes it removes (-0.8 ms) come back as backward-data time (+0.6-0.8 ms:
-            # the extra read of x at ~3 TB/s, narrow N groups re-reading dy), DESIGN.md §6
-            parts = torch.empty((-(-(N * H * W) // 128), 2, Cin), dtype=torch.float32, device=x.device)
-            gred = (x,) + tuple(pro) + (parts,)
-        conv_fwd_raw(dy, wt1, None, dx, N, H, W, Cout, Cin, ks, gred=gred)
-        if gred is not None:
-            _put_bn_parts(dx, gred[-1])
+        conv_fwd_raw(dy, wt1, None, dx, N, H, W, Cout, Cin, ks)
     return dx
 
 
@@ -1096,7 +1056,9 @@ class _ConvBN(torch.autograd.Function):
         M = N * H * W
         dz = dz.contiguous()
         need_dx = ctx.needs_input_grad[0]
-        parts = _take_bn_parts(dz)   # the BN sums a fused depthwise backward already formed
+        # the BatchNorm-backward sums of (dz, y) when the only consumer's fused backward formed them
+        # (a depthwise's, or the next block's 16 -> 96 expand's rod_pw_bwd_gred_rc)
+        parts = _take_bn_parts(dz)
         if ctx.nostore and parts is None:
             raise RuntimeError("expand conv without a stored output: its BatchNorm-backward sums must come from the "
                                "depthwise backward (rod_dw3x3_bwd_fused_rc)")
@@ -1109,10 +1071,7 @@ class _ConvBN(torch.autograd.Function):
             # 16 -> 96 takes the same entry: its input is the previous block's project output, whose
             # linear BatchNorm then gets its sums from here (when dx is that BatchNorm's whole
             # gradient: no residual path adds to it — _take_bn_parts checks)
-            if parts is not None:
-                coef = bn_bwd_coef_from_parts(parts, M, Cout, rstd, gamma, beta, _needs(gamma), _needs(beta))
-            else:
-                coef = bn_bwd_reduce(dz, y, mean, rstd, gamma, beta, ctx.act, _needs(gamma), _needs(beta))
+            coef = _bn_bwd_coef(parts, dz, y, mean, rstd, gamma, beta, ctx.act)
             wt1 = _prep(w, 1, x.dtype, Cout, Cin, 1)
             if dw_pw_ok(ctx.src_dw, x, Cout, ctx.ipro):
                 # the depthwise recomputes dx = dy . W per tile (rod_dw3x3_bwd_fused_pw): hand it
@@ -1137,20 +1096,14 @@ class _ConvBN(torch.autograd.Function):
                 "stembn" not in _DISABLE and _abi.lib().rod_stem_wgrad_bn_supported(Cin, Cout, 3, dtcode(y)):
             # the stem (mobilenet_v2.py:58 + its batch_norm): the weight gradient forms dy from the
             # BatchNorm's (dz, y) in its loader — the [M, 32] dy is never written (rod_stem_wgrad_bn)
-            if parts is not None:
-                coef = bn_bwd_coef_from_parts(parts, M, Cout, rstd, gamma, beta, _needs(gamma), _needs(beta))
-            else:
-                coef = bn_bwd_reduce(dz, y, mean, rstd, gamma, beta, ctx.act, _needs(gamma), _needs(beta))
+            coef = _bn_bwd_coef(parts, dz, y, mean, rstd, gamma, beta, ctx.act)
             ws = workspace(_abi.query("rod_conv_wgrad_workspace", N, H, W, Cin, Cout, 3), x.device)
             _abi.call("rod_stem_wgrad_bn", x, dz, y, mean, rstd, gamma, beta, ctx.act, coef, grad_slot(w), ws, N, H,
                       W, Cin, Cout, 3, dtcode(y), stream())
             _mark_written(w)
             return None, None, None, None, None, None, None
         if ctx.ks == 1 and _pw_fused_ok(M, Cin, Cout, y.dtype) and (need_dx or _needs(w) or _needs(b)):
-            if parts is not None:
-                coef = bn_bwd_coef_from_parts(parts, M, Cout, rstd, gamma, beta, _needs(gamma), _needs(beta))
-            else:
-                coef = bn_bwd_reduce(dz, y, mean, rstd, gamma, beta, ctx.act, _needs(gamma), _needs(beta))
+            coef = _bn_bwd_coef(parts, dz, y, mean, rstd, gamma, beta, ctx.act)
             gw = grad_slot(w) if _needs(w) else torch.empty((Cout, Cin), dtype=torch.float32, device=y.device)
             gb = grad_slot(b) if _needs(b) else None
             wt1 = _prep(w, 1, x.dtype, Cout, Cin, 1) if need_dx else None
@@ -1163,14 +1116,11 @@ class _ConvBN(torch.autograd.Function):
             if _needs(b):
                 _mark_written(b)
         elif ctx.ks == 1 and need_dx and (parts is not None or M > 4096 or SYNC_BN is not None) and \
-                _bwd_data_bn_ok(M, Cout, Cin, y.dtype, ctx.ipro):
+                _bwd_data_bn_ok(M, Cout, Cin, y.dtype):
             # the deep expand convs (64 -> 384, 96 -> 576, 160 -> 960, conv_blocks.py:263-294): the
             # backward-data GEMM forms dy = the BatchNorm-backward apply in its loader and writes it
             # once for the weight gradient (rod_conv_bwd_data_bn) — no rod_bn_bwd_apply launch
-            if parts is not None:
-                coef = bn_bwd_coef_from_parts(parts, M, Cout, rstd, gamma, beta, _needs(gamma), _needs(beta))
-            else:
-                coef = bn_bwd_reduce(dz, y, mean, rstd, gamma, beta, ctx.act, _needs(gamma), _needs(beta))
+            coef = _bn_bwd_coef(parts, dz, y, mean, rstd, gamma, beta, ctx.act)
             dy, dx = conv_bwd_data_bn(dz, y, mean, rstd, gamma, beta, ctx.act, coef, w)
             _conv_bwd_from_dy(x, w, b, ctx.ks, dy, ctx.ipro, False)
         else:
@@ -1229,37 +1179,36 @@ class _DWBN(torch.autograd.Function):
         x, w, y, mean, rstd = ctx.saved_tensors
         gamma, beta = ctx.gb
         N, H, W, C, s, pt, pl, Ho, Wo = ctx.geo
-        # the BatchNorm-backward sums of (dz, y) when the consumer's backward-data formed them
-        # (the project conv's streaming kernel, _conv_bwd_from_dy)
+        # the BatchNorm-backward sums of (dz, y) when the project conv's fused backward formed
+        # them (rod_pw_bwd_gred / rod_pw_bwd_gred_dyp in _ConvBN.backward)
         parts = _take_bn_parts(dz)
         recipe = _take_dz_recipe(dz)   # dz unmaterialised: dy_p, W_p^T of the project (ABI 20)
-        if recipe is not None and _needs(w) and ctx.needs_input_grad[0] and s == 1 and ctx.ipro is not None and \
-                _dw_fused_ok(N, Ho, Wo, C, x.dtype, s):
-            coef = bn_bwd_coef_from_parts(parts, N * Ho * Wo, C, rstd, gamma, beta, _needs(gamma), _needs(beta)) \
-                if parts is not None else None
-            if coef is not None:
-                dyp, wt1, cout = recipe
-                dx = torch.empty_like(x)
-                gparts = torch.empty((_abi.lib().rod_dw3x3_bwd_fused_parts(N, H, W, C, 1, 1, 1), 2, C),
+        fusable = _needs(w) and ctx.needs_input_grad[0] and _dw_fused_ok(N, Ho, Wo, C, x.dtype, s)
+
+        def fused(entry, head, coef, geo):
+            # the three fused entries share their allocations, the arguments from y on and the
+            # tail; head = the entry's own leading arguments, geo = its trailing geometry
+            dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+            gparts = None
+            if ctx.ipro is not None:   # the input BatchNorm's backward sums, handed to its producer
+                gparts = torch.empty((_abi.lib().rod_dw3x3_bwd_fused_parts(N, H, W, C, s, pt, pl), 2, C),
                                      dtype=torch.float32, device=x.device)
-                ws = workspace(_abi.query("rod_dw3x3_bwd_fused_workspace", N, H, W, C, 1, 1, 1), x.device)
-                det = lambda t: None if t is None else t.detach()
-                _abi.call("rod_dw3x3_bwd_fused_pw", x, *_pro_args(ctx.ipro), dyp, wt1, cout, y, mean, rstd,
-                          det(gamma), det(beta), ctx.act, coef, w, dx, grad_slot(w), gparts, ws, N, H, W, C,
-                          dtcode(x), stream())
-                _mark_written(w)
+            ws = workspace(_abi.query("rod_dw3x3_bwd_fused_workspace", N, H, W, C, s, pt, pl), x.device)
+            _abi.call(entry, *head, y, mean, rstd, _det(gamma), _det(beta), ctx.act, coef, w, dx, grad_slot(w),
+                      gparts, ws, N, H, W, C, *geo, dtcode(x), stream())
+            _mark_written(w)
+            if gparts is not None:
                 _put_bn_parts(dx, gparts)
-                return dx, None, None, None, None
+            return dx, None, None, None, None
+        if recipe is not None and parts is not None and fusable and s == 1 and ctx.ipro is not None:
+            # dz recomputed per tile from dy_p (rod_dw3x3_bwd_fused_pw; stride 1: pt = pl = 1)
+            coef = _bn_bwd_coef(parts, None, y, mean, rstd, gamma, beta, ctx.act)
+            return fused("rod_dw3x3_bwd_fused_pw", (x, *_pro_args(ctx.ipro), *recipe), coef, ())
         if recipe is not None:   # any other path: the dz the project would have written
             dz = _materialize_dz(recipe, (N, Ho, Wo, C), y.dtype)
             if parts is not None:
                 _put_bn_parts(dz, parts)
                 parts = _take_bn_parts(dz)
-
-        def coef_d():
-            if parts is not None:
-                return bn_bwd_coef_from_parts(parts, N * Ho * Wo, C, rstd, gamma, beta, _needs(gamma), _needs(beta))
-            return bn_bwd_reduce(dz, y, mean, rstd, gamma, beta, ctx.act, _needs(gamma), _needs(beta))
         if ctx.rc_src is not None:
             # the input (the expand's output) was never written: the stride-2 fused backward
             # recomputes it from the block input (ABI 23)
@@ -1267,67 +1216,24 @@ class _DWBN(torch.autograd.Function):
                 raise RuntimeError("depthwise over an unwritten expand output needs the fused stride-2 backward")
             xin, xpro, wt0, Cin = ctx.rc_src
             dz = dz.contiguous()
-            coef = coef_d()
-            dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-            gparts = torch.empty((_abi.lib().rod_dw3x3_bwd_fused_parts(N, H, W, C, s, pt, pl), 2, C),
-                                 dtype=torch.float32, device=x.device)
-            ws = workspace(_abi.query("rod_dw3x3_bwd_fused_workspace", N, H, W, C, s, pt, pl), x.device)
-            det = lambda t: None if t is None else t.detach()
-            _abi.call("rod_dw3x3_bwd_fused_rc", xin, *_pro_args(xpro), wt0, Cin, *_pro_args(ctx.ipro), dz, y, mean, rstd,
-                      det(gamma), det(beta), ctx.act, coef, w, dx, grad_slot(w), gparts, ws, N, H, W, C, s, pt, pl,
-                      Ho, Wo, dtcode(dz), stream())
-            _mark_written(w)
-            _put_bn_parts(dx, gparts)
-            return dx, None, None, None, None
-        if _needs(w) and ctx.needs_input_grad[0] and _dw_fused_ok(N, Ho, Wo, C, x.dtype, s):
+            coef = _bn_bwd_coef(parts, dz, y, mean, rstd, gamma, beta, ctx.act)
+            return fused("rod_dw3x3_bwd_fused_rc", (xin, *_pro_args(xpro), wt0, Cin, *_pro_args(ctx.ipro), dz), coef,
+                         (s, pt, pl, Ho, Wo))
+        if fusable:
             # one pass: BN_d backward apply + backward-data + filter gradient (+ the input
-            # BatchNorm's backward sums, handed to the producer) — rod_dw3x3_bwd_fused
-            # (ABI 12 stride 1, ABI 13 stride 2)
+            # BatchNorm's backward sums) — rod_dw3x3_bwd_fused (ABI 12 stride 1, ABI 13 stride 2)
             dz = dz.contiguous()
-            coef = coef_d()
-            dx = torch.empty_like(x)
-            gparts = None
-            if ctx.ipro is not None:
-                gparts = torch.empty((_abi.lib().rod_dw3x3_bwd_fused_parts(N, H, W, C, s, pt, pl), 2, C),
-                                     dtype=torch.float32, device=x.device)
-            ws = workspace(_abi.query("rod_dw3x3_bwd_fused_workspace", N, H, W, C, s, pt, pl), x.device)
-            det = lambda t: None if t is None else t.detach()
-            _abi.call("rod_dw3x3_bwd_fused", x, *_pro_args(ctx.ipro), dz, y, mean, rstd, det(gamma), det(beta),
-                      ctx.act, coef, w, dx, grad_slot(w), gparts, ws, N, H, W, C, s, pt, pl, Ho, Wo, dtcode(x),
-                      stream())
-            _mark_written(w)
-            if gparts is not None:
-                _put_bn_parts(dx, gparts)
-            return dx, None, None, None, None
-        if _needs(w) and N * Ho * Wo > 4096 and "dwbn" in _ENABLE:
-            # opt-in (ROD_ENABLE=dwbn): the BatchNorm-backward apply runs inside the filter
-            # gradient, which writes dy for the backward-data pass (rod_dw3x3_bwd_filter_bn).
-            # Bit-identical, but measured no faster per step: the apply pass it
-            # removes (-1.59 ms) comes back as filter-gradient time (+1.22 ms, VALU-bound)
-            dz = dz.contiguous()
-            coef = coef_d()
-            dy = torch.empty_like(y)
-            ws = workspace(_abi.query("rod_dw3x3_bwd_filter_workspace", N, Ho, Wo, C), x.device)
-            det = lambda t: None if t is None else t.detach()
-            _abi.call("rod_dw3x3_bwd_filter_bn", x, *_pro_args(ctx.ipro), dz, y, mean, rstd, det(gamma), det(beta),
-                      ctx.act, coef, dy, grad_slot(w), ws, N, H, W, C, s, pt, pl, Ho, Wo, dtcode(x), stream())
-            _mark_written(w)
-            dx = None
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
-                _abi.call("rod_dw3x3_bwd_data", dy, w, dx, *_gred_args(None), N, H, W, C, s, pt, pl, Ho, Wo,
-                          dtcode(x), stream())
-            return dx, None, None, None, None
+            coef = _bn_bwd_coef(parts, dz, y, mean, rstd, gamma, beta, ctx.act)
+            return fused("rod_dw3x3_bwd_fused", (x, *_pro_args(ctx.ipro), dz), coef, (s, pt, pl, Ho, Wo))
         if parts is not None:
-            dy = _bn_bwd_apply(dz, y, mean, rstd, gamma, beta, ctx.act, coef_d())
+            coef = _bn_bwd_coef(parts, dz, y, mean, rstd, gamma, beta, ctx.act)
+            dy = _bn_bwd_apply(dz, y, mean, rstd, gamma, beta, ctx.act, coef)
         else:
             dy = bn_bwd_dy(dz, y, mean, rstd, gamma, beta, ctx.act, _needs(gamma), _needs(beta))
         if _needs(w):
-            def filt():
-                ws = workspace(_abi.query("rod_dw3x3_bwd_filter_workspace", N, Ho, Wo, C), x.device)
-                _abi.call("rod_dw3x3_bwd_filter", x, *_pro_args(ctx.ipro), dy, grad_slot(w), ws, N, H, W, C, s, pt,
-                          pl, Ho, Wo, dtcode(x), stream())
-            SIDE.run(filt, x, dy, ctx.ipro)
+            ws = workspace(_abi.query("rod_dw3x3_bwd_filter_workspace", N, Ho, Wo, C), x.device)
+            _abi.call("rod_dw3x3_bwd_filter", x, *_pro_args(ctx.ipro), dy, grad_slot(w), ws, N, H, W, C, s, pt, pl,
+                      Ho, Wo, dtcode(x), stream())
             _mark_written(w)
         dx = None
         if ctx.needs_input_grad[0]:
@@ -1355,8 +1261,7 @@ def _in_pro(x):
     if isinstance(x, Pending):
         if not x.owned:
             raise ValueError("conv2d_bn / dw3x3_bn take plain tensors or owned Pendings")
-        det = lambda t: None if t is None else t.detach()
-        return x.y, (x.mean, x.rstd, det(x.gamma), det(x.beta), x.act)
+        return x.y, (x.mean, x.rstd, _det(x.gamma), _det(x.beta), x.act)
     return x, None
 
 
@@ -1427,11 +1332,9 @@ def conv2d_bn_act(x, w, b, ksize, gamma, beta, mmean, mvar, act, training, decay
         wt = _prep(w, 0, xt.dtype, Cout, Cin, ksize)
     z = torch.empty((N, H, W, Cout), dtype=xt.dtype, device=xt.device)
     mean, rstd = bn_statistics(z, mmean, mvar, False, decay, eps)
-    nb = 0 if "splitk" in _DISABLE else _abi.query("rod_conv_fwd_workspace", N, H, W, Cin, Cout, ksize)
-    ws = workspace(nb, xt.device) if nb else None
+    ws = _splitk_ws(xt.device, N, H, W, Cin, Cout, ksize)
     res = residual.contiguous() if residual is not None else None
-    det = lambda t: None if t is None else t.detach()
-    _abi.call("rod_conv_fwd_bnact", xt, *_pro_args(ipro), wt, det(b), z, ws, mean, rstd, det(gamma), det(beta), act,
+    _abi.call("rod_conv_fwd_bnact", xt, *_pro_args(ipro), wt, _det(b), z, ws, mean, rstd, _det(gamma), _det(beta), act,
               res, 0, N, H, W, Cin, Cout, ksize, 0, 0, dtcode(xt), stream())
     return z
 

@@ -74,10 +74,6 @@ class Trainer:
                                         comm=getattr(reducer, 'comm', None))
         else:
             ops.SYNC_BN = None
-        # weight gradients beside the backward-data chain (opt-in, ROD_ENABLE=side; single
-        # process only: under DP the gradient buckets are reduced from inside backward).
-        # Measured slower: 24.42 -> 24.93 ms per graphed step
-        self._side = world_size == 1 and reducer is None and "side" in ops._ENABLE
         rank = torch.distributed.get_rank() if world_size > 1 and torch.distributed.is_initialized() else 0
         ops.DROPOUT_RANK[:] = [rank, world_size]
         self._eager_steps = 0
@@ -97,15 +93,12 @@ class Trainer:
         calls = ops._DROPOUT_CALLS[0]
         losses = self.losses(img_u8, gt_corner, gt_labels, gt_n)
         self._dropout_seen |= ops._DROPOUT_CALLS[0] != calls
-        if self._side:
-            ops.SIDE.backward(losses[0], self.device)
-        else:
-            # the weight-gradient slab sums are batched into a few launches at the end
-            ops.SLAB.begin()
-            try:
-                graph.backward(losses[0])
-            finally:
-                ops.SLAB.end()
+        # the weight-gradient slab sums are batched into a few launches at the end
+        ops.SLAB.begin()
+        try:
+            graph.backward(losses[0])
+        finally:
+            ops.SLAB.end()
         return losses
 
     def graph_mode(self):

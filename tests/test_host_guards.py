@@ -7,8 +7,10 @@
     data set on one device, dataset/pascalvoc_common.py:40-107);
   * the dropout seed differs per rank (ops.dropout);
   * ParamStore.eval_views serves a BatchNorm's eval slices only for buffers that really are
-    views of the flat moving-statistics buffer.
+    views of the flat moving-statistics buffer;
+  * ROD_DISABLE / ROD_ENABLE tokens the code does not read are rejected (ops._switches).
 """
+import os
 import struct
 
 import numpy as np
@@ -134,3 +136,35 @@ def test_bn_parts_handoff_rejects_summed_gradient():
     ops._put_bn_parts(dx, parts)
     assert ops._take_bn_parts(dx.view(4, 8)) is parts   # a view of the same, unchanged storage
     ops.clear_bn_parts()
+
+
+def test_switches_reject_unknown_tokens():
+    """ops._switches: the known tokens parse, an empty value is the empty set, and a token the
+    code does not read — a retired path (gred, side) or a misspelling — raises, naming it."""
+    assert ops._switches('rc', ops._DISABLE_KNOWN) == {'rc'}
+    assert ops._switches('nostore,rc,dwfused2', ops._DISABLE_KNOWN) == {'nostore', 'rc', 'dwfused2'}
+    assert ops._switches('rcdw', ops._ENABLE_KNOWN) == {'rcdw'}
+    assert ops._switches('', ops._DISABLE_KNOWN) == set()
+    assert ops._switches('', ops._ENABLE_KNOWN) == set()
+    for known in (ops._ENABLE_KNOWN, ops._DISABLE_KNOWN):
+        for bad in ('gred', 'side', 'gredpw', 'dwbn', 'rc144', 'nostroe'):
+            with pytest.raises(ValueError, match=repr(bad)):
+                ops._switches(bad, known)
+            with pytest.raises(ValueError, match=repr(bad)):
+                ops._switches(known[0] + ',' + bad, known)
+    # a switch of one variable is not a switch of the other
+    with pytest.raises(ValueError, match="'rcinf1'"):
+        ops._switches('rcinf1', ops._ENABLE_KNOWN)
+    # the live sets are plain sets (tests and tools add / discard tokens in place)
+    assert type(ops._DISABLE) is set and type(ops._ENABLE) is set
+    # every token some module reads from the live sets is registered
+    import re
+    root = os.path.join(os.path.dirname(os.path.abspath(ops.__file__)), '..')
+    read = {'_DISABLE': set(), '_ENABLE': set()}
+    for d in ('rod', 'nets', os.path.join('nets', 'backbone')):
+        for f in os.listdir(os.path.join(root, d)):
+            if f.endswith('.py'):
+                src = open(os.path.join(root, d, f)).read()
+                for tok, var in re.findall(r"""["'](\w+)["'] (?:not )?in (?:ops\.)?(_DISABLE|_ENABLE)\b""", src):
+                    read[var].add(tok)
+    assert read['_DISABLE'] == set(ops._DISABLE_KNOWN) and read['_ENABLE'] == set(ops._ENABLE_KNOWN), read

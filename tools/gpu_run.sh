@@ -29,7 +29,7 @@ for step in "$@"; do
   case $step in
     rcinf) run rcinftest 300 python -u -m pytest tests/test_gpu_recompute.py -k predict -m gpu -v --timeout 240 --timeout-method thread -p no:cacheprovider &&
          for i in 1 2; do run pinf0_$i 200 env ROD_DISABLE=rcinf python tools/predict_bench.py --res 1080 --batch 8 --iters 30 && run pinf1_$i 200 python tools/predict_bench.py --res 1080 --batch 8 --iters 30 && run pinf720_0_$i 200 env ROD_DISABLE=rcinf python tools/predict_bench.py --res 720 --batch 32 --iters 20 && run pinf720_1_$i 200 python tools/predict_bench.py --res 720 --batch 32 --iters 20; done; grep -H ms_per_batch $OUT/${TAG}_pinf*.log ;;
-    rcinfab) for i in 1 2; do for cfg in "" "ROD_DISABLE=irblock" "ROD_DISABLE=irblock ROD_ENABLE=rcinf1"; do n=$(echo "$cfg" | tr -c 'a-z0-9\n' '_'); run pq${n}_$i 200 env $cfg python tools/predict_bench.py --res 1080 --batch 8 --iters 30 && run pq720${n}_$i 200 env $cfg python tools/predict_bench.py --res 720 --batch 32 --iters 20; done; done; grep -H ms_per_batch $OUT/${TAG}_pq*.log ;;
+    rcinfab) for i in 1 2; do for cfg in "" "ROD_DISABLE=irblock" "ROD_DISABLE=irblock,rcinf1"; do n=$(echo "$cfg" | tr -c 'a-z0-9\n' '_'); run pq${n}_$i 200 env $cfg python tools/predict_bench.py --res 1080 --batch 8 --iters 30 && run pq720${n}_$i 200 env $cfg python tools/predict_bench.py --res 720 --batch 32 --iters 20; done; done; grep -H ms_per_batch $OUT/${TAG}_pq*.log ;;
     rcfwdab) run rcfwdtest 400 python -u -m pytest tests/test_gpu_recompute.py tests/test_gpu_irblock.py -k "dw3x3_fwd_rc or predict or step or backbone" -m gpu -v --timeout 300 --timeout-method thread -p no:cacheprovider &&
          run rcb_prev 200 env ROD_LIB=road-object-detection-for-bdd100k_amd/lib/librod_prev.so python tools/rc_bench.py b1 b2 b3 b6 && run rcb_new 200 python tools/rc_bench.py b1 b2 b3 b6 && run rcb_narrow 200 env ROD_STATS_NARROW=1 python tools/rc_bench.py b1 b3 &&
          for i in 1 2; do run pr0_$i 200 env ROD_LIB=road-object-detection-for-bdd100k_amd/lib/librod_prev.so python tools/predict_bench.py --res 1080 --batch 8 --iters 30 && run pr1_$i 200 python tools/predict_bench.py --res 1080 --batch 8 --iters 30; done &&
@@ -62,9 +62,6 @@ for step in "$@"; do
     trprev2) run trtest2 400 python -u -m pytest tests/test_gpu_recompute.py tests/test_gpu_pwbwd.py -m gpu -q --timeout 300 --timeout-method thread -p no:cacheprovider &&
          for i in 1 2; do run tq0_$i 300 env ROD_LIB=road-object-detection-for-bdd100k_amd/lib/librod_prev.so python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run tq1_$i 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0; done;
          grep -H -o '"value": [0-9.]*' $OUT/${TAG}_tq?_*.log ;;
-    sepi) run sepitest 400 python -u -m pytest tests/test_gpu_bnepi.py tests/test_gpu_recompute.py -k "predict" -m gpu -v --timeout 300 --timeout-method thread -p no:cacheprovider &&
-         for i in 1 2; do run se0_$i 200 env ROD_DISABLE=streamepi python tools/predict_bench.py --res 1080 --batch 8 --iters 30 && run se1_$i 200 python tools/predict_bench.py --res 1080 --batch 8 --iters 30 && run sf0_$i 200 env ROD_DISABLE=streamepi python tools/predict_bench.py --res 720 --batch 32 --iters 20 && run sf1_$i 200 python tools/predict_bench.py --res 720 --batch 32 --iters 20; done;
-         grep -H ms_per_batch $OUT/${TAG}_se?_*.log $OUT/${TAG}_sf?_*.log ;;
     bnsmall) for v in 4 2 1; do run bnsmall_$v 200 env ROD_BN_SMALL_CVB=$v python tools/bn_bench.py --iters 20; done; grep -H -E "M= *(1920|480|120) |TOTAL" $OUT/${TAG}_bnsmall_*.log ;;
     tests) run tests 900 python -m pytest tests -m gpu -q -x --timeout=600 -p no:cacheprovider ;;
     testsall) run testsall 900 python -m pytest tests -m gpu -q --timeout=600 -p no:cacheprovider ;;
@@ -89,9 +86,6 @@ for step in "$@"; do
     bench) run bench 600 python bench.py --full --steps 10 --warmup 3 ;;
     benchfast) run benchfast 400 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline ;;
     benchfp32) run benchfp32 600 python bench.py --full --dtype fp32 --steps 5 --warmup 2 --no-cpu-baseline --no-inference ;;
-    benchgred) run benchgred 400 env ROD_ENABLE=gred python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-inference --kernel-steps 0 &&
-               run benchbase 400 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-inference --kernel-steps 0 &&
-               run benchgreddw 400 env ROD_ENABLE=gred,dwbn python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-inference --kernel-steps 0 ;;
     hosttime) run hosttime 300 python tools/host_time.py --steps 10 ;;
     hostprof) run hostprof 300 python -m cProfile -s tottime tools/host_time.py --steps 5 ;;
     bnu) run bnu4 300 python tools/bn_bench.py --out /tmp/${TAG}_bn4.pt && run bnu8 300 env ROD_BN_RED_U=8 python tools/bn_bench.py --check /tmp/${TAG}_bn4.pt ;;
