@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ROD_ABI_VERSION 23
+#define ROD_ABI_VERSION 24
 #define ROD_EINVAL (-1)
 
 enum { ROD_F32 = 0, ROD_BF16 = 1, ROD_I32 = 2 /* collectives only (ABI 19) */ };
@@ -662,6 +662,50 @@ int rod_select_topk_nms(const float* probs, const float* boxes, int B, int A, in
  * Plain SGD with clip by value (net_tools.py:645-651):
  *   p -= lr * clamp(g, -clip, clip)   over one flat fp32 buffer. */
 int rod_sgd_clip(float* param, const float* grad, long n, float lr, float clip, void* stream);
+
+/* Momentum SGD with weight decay, norm clipping and a device-resident rate (ABI 24).  Extends the
+ * reference's optimizer op (net_tools.py:626-654: clip by value, then ApplyGradientDescent) with
+ * what it lacks; rod_sgd_clip stays the default step.
+ *
+ * flags: one byte per group of 4 consecutive elements (n % 4 == 0; the flat parameter buffer
+ * aligns every variable to 4 elements, so a group never straddles two variables):
+ *   bit 0 (ROD_OPT_TRAINABLE)  the group is updated / counted in the norm;
+ *   bit 1 (ROD_OPT_DECAY)      weight decay applies to the group.
+ * Alignment padding has flags 0.
+ *
+ * rod_grad_sqnorm: norm = sqrt(sum g^2) over the trainable groups, and
+ *     *scale = min(1, clip_norm / max(norm, FLT_MIN))          (clip_norm > 0)
+ * written to device memory (nothing returns to the host).  A NaN or Inf norm gives a NaN scale.
+ * Deterministic, fp32, no atomics, in two launches with a partition that depends on n alone:
+ *   stage 1  thread t of block b (256 threads, at most 1024 blocks) takes the groups
+ *            b*256 + t + k*262144, k = 0, 1, ... in order, one running sum per element lane
+ *            (s_j = s_j + g_j*g_j), then (s0 + s1) + (s2 + s3), then the block's 256 values are
+ *            halved 8 times (x[t] = x[t] + x[t + w], w = 128 ... 1) into parts[b];
+ *   stage 2  one block: thread t forms (parts[t] + parts[t+256]) + (parts[t+512] + parts[t+768])
+ *            (absent parts are 0), the same 8 halvings, sqrt, scale.
+ * workspace: rod_grad_sqnorm_workspace() bytes, 4-byte aligned.
+ *
+ * rod_sgd_momentum: one launch over the flat buffer, 16-byte loads and stores; per element of a
+ * trainable group, each line one fp32 operation rounded on its own, in this order:
+ *     d = g
+ *     d = d * *scale                       only when scale != NULL (norm clipping on)
+ *     d = clip(d, -clip, clip)             NaN stays NaN, as in rod_sgd_clip; clip = +inf: off
+ *     d = d + wd * p                       only in groups with ROD_OPT_DECAY
+ *     m = mu * m + d                       mom == NULL (allowed when mu == 0): m = d, not stored
+ *     u = nesterov ? d + mu * m : m
+ *     p = p - *lr * u
+ * (clip, then decay: the order of torch.nn.utils.clip_grad_* followed by
+ * torch.optim.SGD(weight_decay=...).)  lr and scale are read from device memory, so a captured
+ * graph applies whatever rate the host last wrote and the scale rod_grad_sqnorm just produced.
+ * Groups without ROD_OPT_TRAINABLE are not touched: neither param nor mom is read or written,
+ * whatever grad holds there.  param, grad and mom are 16-byte aligned. */
+enum { ROD_OPT_TRAINABLE = 1, ROD_OPT_DECAY = 2 };
+size_t rod_grad_sqnorm_workspace(void);
+int rod_grad_sqnorm(const float* grad, const unsigned char* flags, long n, float clip_norm,
+                    float* scale, void* workspace, void* stream);
+int rod_sgd_momentum(float* param, const float* grad, float* mom, const unsigned char* flags, long n,
+                     const float* lr, const float* scale, float mu, float wd, float clip,
+                     int nesterov, void* stream);
 
 /* ------------------------------------------------ deferred parameter-gradient sums (ABI 11)
  * The weight / bias gradients of rod_conv_wgrad, rod_dw3x3_bwd_filter(_bn) and rod_pw_bwd end in

@@ -1,4 +1,5 @@
 // api.hip — error reporting, version, and small elementwise entry points.
+#include <float.h>
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -243,6 +244,93 @@ __global__ void sgd_clip_kernel(float* __restrict__ p, const float* __restrict__
   }
 }
 
+// ---- momentum SGD over the flat buffer (rod_sgd_momentum; the formula and its order are the
+// contract in include/rod.h; -ffp-contract=off keeps every line one rounded operation).
+// One thread per group of 4 elements per pass: one flag byte, three 16-byte loads, two 16-byte
+// stores.  A group without ROD_OPT_TRAINABLE costs its flag byte only.
+__global__ void __launch_bounds__(256) sgd_momentum_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                           float* __restrict__ m,
+                                                           const uint8_t* __restrict__ flags, long ngroups,
+                                                           const float* __restrict__ lr_p,
+                                                           const float* __restrict__ scale_p, float mu, float wd,
+                                                           float clip, int nesterov) {
+  const float lr = *lr_p;
+  const float scale = scale_p ? *scale_p : 1.0f;
+  long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (; q < ngroups; q += stride) {
+    const unsigned f = flags[q];
+    if (!(f & ROD_OPT_TRAINABLE)) continue;
+    const long i = q * 4;
+    f32x4 pv = *(f32x4*)(p + i);
+    const f32x4 gv = *(const f32x4*)(g + i);
+    f32x4 mv = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (m) mv = *(f32x4*)(m + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float d = gv[j];
+      if (scale_p) d = d * scale;                    // global-norm clip (scale from rod_grad_sqnorm)
+      d = clip_tf(d, clip);                          // tf.clip_by_value
+      if (f & ROD_OPT_DECAY) d = d + wd * pv[j];
+      const float mj = m ? mu * mv[j] + d : d;
+      const float u = nesterov ? d + mu * mj : mj;
+      pv[j] = pv[j] - lr * u;
+      mv[j] = mj;
+    }
+    *(f32x4*)(p + i) = pv;
+    if (m) *(f32x4*)(m + i) = mv;
+  }
+}
+
+// ---- sum of squares of the trainable gradient (rod_grad_sqnorm): the partition is a function
+// of n alone (stride SQN_PARTS * 256 groups whatever the grid), every sum has a fixed order.
+constexpr int SQN_PARTS = 1024;
+
+__device__ __forceinline__ float block_tree_sum(float v, float* red) {
+  const int t = threadIdx.x;
+  red[t] = v;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) red[t] = red[t] + red[t + w];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+__global__ void __launch_bounds__(256) grad_sqnorm_parts_kernel(const float* __restrict__ g,
+                                                                const uint8_t* __restrict__ flags, long ngroups,
+                                                                float* __restrict__ parts) {
+  __shared__ float red[256];
+  float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < ngroups; q += (long)SQN_PARTS * 256) {
+    if (!(flags[q] & ROD_OPT_TRAINABLE)) continue;
+    const f32x4 v = *(const f32x4*)(g + q * 4);
+    s0 = s0 + v[0] * v[0];
+    s1 = s1 + v[1] * v[1];
+    s2 = s2 + v[2] * v[2];
+    s3 = s3 + v[3] * v[3];
+  }
+  const float s = block_tree_sum((s0 + s1) + (s2 + s3), red);
+  if (threadIdx.x == 0) parts[blockIdx.x] = s;
+}
+
+__global__ void __launch_bounds__(256) grad_sqnorm_final_kernel(const float* __restrict__ parts, int nparts,
+                                                                float clip_norm, float* __restrict__ scale) {
+  __shared__ float red[256];
+  const int t = threadIdx.x;
+  float a[SQN_PARTS / 256];
+#pragma unroll
+  for (int k = 0; k < SQN_PARTS / 256; ++k) a[k] = t + 256 * k < nparts ? parts[t + 256 * k] : 0.0f;
+  static_assert(SQN_PARTS == 1024, "stage 2 pairs four parts per thread");
+  const float s = block_tree_sum((a[0] + a[1]) + (a[2] + a[3]), red);
+  if (t == 0) {
+    const float norm = sqrtf(s);
+    const float r = clip_norm / fmaxf(norm, FLT_MIN);
+    // a NaN or Inf gradient poisons the update (fmaxf / fminf would drop the NaN)
+    *scale = !(norm <= FLT_MAX) ? __builtin_nanf("") : (r < 1.0f ? r : 1.0f);
+  }
+}
+
 }  // namespace rod
 
 using namespace rod;
@@ -351,6 +439,49 @@ int rod_sgd_clip(float* param, const float* grad, long n, float lr, float clip, 
   hipLaunchKernelGGL(sgd_clip_kernel, dim3(blocks), dim3(256), 0, ROD_STREAM(stream), param, grad, n,
                      lr, clip);
   return check_launch("rod_sgd_clip");
+}
+
+size_t rod_grad_sqnorm_workspace(void) { return SQN_PARTS * sizeof(float); }
+
+int rod_grad_sqnorm(const float* grad, const unsigned char* flags, long n, float clip_norm, float* scale,
+                    void* workspace, void* stream) {
+  ROD_CHECK_ARG(n >= 0 && n % 4 == 0, "rod_grad_sqnorm: n must be a non-negative multiple of 4");
+  ROD_CHECK_ARG(((uintptr_t)grad & 15) == 0, "rod_grad_sqnorm: grad must be 16-byte aligned");
+  ROD_CHECK_ARG(clip_norm > 0.0f, "rod_grad_sqnorm: clip_norm must be > 0");
+  ROD_CHECK_ARG(scale != nullptr && workspace != nullptr && ((uintptr_t)workspace & 3) == 0,
+                "rod_grad_sqnorm: scale and a 4-byte aligned workspace are required");
+  ROD_CHECK_ARG(n == 0 || (grad != nullptr && flags != nullptr), "rod_grad_sqnorm: grad and flags are required");
+  hipStream_t s = ROD_STREAM(stream);
+  const long ngroups = n / 4;
+  const int nparts = (int)std::min<long>(cdivl(ngroups, 256), SQN_PARTS);
+  if (nparts > 0) {
+    hipLaunchKernelGGL(grad_sqnorm_parts_kernel, dim3(nparts), dim3(256), 0, s, grad, (const uint8_t*)flags,
+                       ngroups, (float*)workspace);
+    const int rc = check_launch("rod_grad_sqnorm");
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(grad_sqnorm_final_kernel, dim3(1), dim3(256), 0, s, (const float*)workspace, nparts,
+                     clip_norm, scale);
+  return check_launch("rod_grad_sqnorm");
+}
+
+int rod_sgd_momentum(float* param, const float* grad, float* mom, const unsigned char* flags, long n,
+                     const float* lr, const float* scale, float mu, float wd, float clip, int nesterov,
+                     void* stream) {
+  ROD_CHECK_ARG(n >= 0 && n % 4 == 0, "rod_sgd_momentum: n must be a non-negative multiple of 4");
+  ROD_CHECK_ARG(((uintptr_t)param & 15) == 0 && ((uintptr_t)grad & 15) == 0 && ((uintptr_t)mom & 15) == 0,
+                "rod_sgd_momentum: buffers must be 16-byte aligned");
+  ROD_CHECK_ARG(lr != nullptr, "rod_sgd_momentum: lr (device pointer) is required");
+  ROD_CHECK_ARG(mom != nullptr || mu == 0.0f, "rod_sgd_momentum: mu != 0 needs the momentum buffer");
+  ROD_CHECK_ARG(!(clip < 0.0f) && clip == clip, "rod_sgd_momentum: clip must be >= 0 (+inf disables it)");
+  if (n == 0) return 0;
+  ROD_CHECK_ARG(param != nullptr && grad != nullptr && flags != nullptr,
+                "rod_sgd_momentum: param, grad and flags are required");
+  const long ngroups = n / 4;
+  int blocks = (int)std::min<long>(cdivl(ngroups, 256), 4096);
+  hipLaunchKernelGGL(sgd_momentum_kernel, dim3(blocks), dim3(256), 0, ROD_STREAM(stream), param, grad, mom,
+                     (const uint8_t*)flags, ngroups, lr, scale, mu, wd, clip, nesterov);
+  return check_launch("rod_sgd_momentum");
 }
 
 }  // extern "C"

@@ -304,31 +304,51 @@ def store_to_tf_layout(name, a):
     return a
 
 
-def load_variables(store, path, names_regex=None):
-    """Restore a ParamStore from a torch checkpoint or a TF tensor bundle; returns global_step.
-    names_regex: restore only matching names (the reference's restore_saver filter)."""
+MOMENTUM_SLOT = '/Momentum'   # tf.train.MomentumOptimizer's slot name: <variable>/Momentum
+
+
+def load_variables(store, path, names_regex=None, optimizer=None):
+    """Restore a ParamStore from a torch checkpoint or a TF tensor bundle; returns global_step
+    (which drives the optimiser's schedule: the caller sets optimizer.global_step to it).
+    names_regex: restore only matching names (the reference's restore_saver filter).
+    optimizer: a net_tools.optimizer whose momentum is restored with the variables (zero for a
+    variable the checkpoint holds no momentum of); one without state ignores a stored state."""
     if is_tf_bundle(path):
         tf = read_tf_bundle(path)
         step = int(np.asarray(tf.get('global_step', 0)).reshape(-1)[0]) if 'global_step' in tf else 0
-        sd = {}
+        sd, mom = {}, {}
         for n, t in list(store.params.items()) + list(store.buffers.items()):
             if n in tf:
                 sd[n] = torch.from_numpy(tf_to_store_layout(n, tf[n], t.shape))
+            if n + MOMENTUM_SLOT in tf and n in store.params:
+                mom[n] = torch.from_numpy(tf_to_store_layout(n, tf[n + MOMENTUM_SLOT], t.shape))
         store.load_state_dict(sd, strict=names_regex is None, names_regex=names_regex)
+        if optimizer is not None:
+            optimizer.load_state_dict(mom, names_regex=names_regex)
         return step
     if not os.path.isfile(path):
         raise FileNotFoundError('checkpoint %r not found' % path)
     sd = torch.load(path, map_location='cpu', weights_only=True)
     store.load_state_dict(sd['variables'], strict=names_regex is None, names_regex=names_regex)
+    if optimizer is not None:
+        optimizer.load_state_dict(sd.get('optimizer', {}), names_regex=names_regex)
     return int(sd.get('global_step', 0))
 
 
-def save_variables(store, path, step, fmt='torch'):
-    """fmt 'torch' (default, what train.py writes) or 'tf' (a tensor bundle at prefix `path`)."""
+def save_variables(store, path, step, fmt='torch', optimizer=None):
+    """fmt 'torch' (default, what train.py writes) or 'tf' (a tensor bundle at prefix `path`).
+    optimizer: a net_tools.optimizer; its momentum (if it keeps one) is saved per variable, as
+    the entry 'optimizer' {name: tensor} beside 'variables' (torch) or as slots named
+    <variable>/Momentum in the variable's own TF layout (tf)."""
     os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
+    mom = optimizer.state_dict() if optimizer is not None else {}
     if fmt == 'tf':
         t = {n: store_to_tf_layout(n, v.numpy()) for n, v in store.state_dict().items()}
+        t.update({n + MOMENTUM_SLOT: store_to_tf_layout(n, v.numpy()) for n, v in mom.items()})
         t['global_step'] = np.array(step, np.int64)
         write_tf_bundle(path, t)
         return
-    torch.save({'variables': store.state_dict(), 'global_step': step}, path)
+    ck = {'variables': store.state_dict(), 'global_step': step}
+    if mom:
+        ck['optimizer'] = mom
+    torch.save(ck, path)

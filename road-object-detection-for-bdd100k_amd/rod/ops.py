@@ -1538,6 +1538,33 @@ def sgd_clip_(param_flat: torch.Tensor, grad_flat: torch.Tensor, lr: float, clip
     _abi.call("rod_sgd_clip", param_flat, grad_flat, param_flat.numel(), float(lr), float(clip), stream())
 
 
+def grad_sqnorm_workspace(device) -> torch.Tensor:
+    """The partial-sum workspace of rod_grad_sqnorm (a caller allocation, reusable across calls)."""
+    return torch.empty(_abi.query("rod_grad_sqnorm_workspace") // 4, dtype=torch.float32, device=device)
+
+
+def grad_sqnorm_(grad_flat: torch.Tensor, flags: torch.Tensor, clip_norm: float, scale: torch.Tensor,
+                 workspace: torch.Tensor):
+    """scale[0] = min(1, clip_norm / |g|) over the trainable groups of the flat gradient, on the
+    device (rod_grad_sqnorm: deterministic, NaN for a NaN / Inf gradient)."""
+    assert flags.dtype == torch.uint8 and flags.numel() * 4 == grad_flat.numel()
+    assert scale.dtype == torch.float32 and workspace.numel() * 4 >= _abi.query("rod_grad_sqnorm_workspace")
+    _abi.call("rod_grad_sqnorm", grad_flat, flags, grad_flat.numel(), float(clip_norm), scale, workspace, stream())
+
+
+def sgd_momentum_(param_flat: torch.Tensor, grad_flat: torch.Tensor, mom_flat, flags: torch.Tensor,
+                  lr: torch.Tensor, scale=None, mu: float = 0.0, wd: float = 0.0, clip: float = math.inf,
+                  nesterov: bool = False):
+    """rod_sgd_momentum over the flat buffers (formula in include/rod.h).  lr and scale are
+    one-element fp32 DEVICE tensors (scale None: no norm clipping); mom_flat may be None only
+    with mu == 0; flags holds one uint8 per 4 elements (ParamStore.group_flags)."""
+    assert flags.dtype == torch.uint8 and flags.numel() * 4 == param_flat.numel() == grad_flat.numel()
+    assert lr.dtype == torch.float32 and (scale is None or scale.dtype == torch.float32)
+    assert mom_flat is None or (mom_flat.dtype == torch.float32 and mom_flat.numel() == param_flat.numel())
+    _abi.call("rod_sgd_momentum", param_flat, grad_flat, mom_flat, flags, param_flat.numel(), lr, scale, float(mu),
+              float(wd), float(clip), 1 if nesterov else 0, stream())
+
+
 # ----------------------------------------------------------------------------- deconv pyramid
 class _Resize(torch.autograd.Function):
     @staticmethod

@@ -15,11 +15,22 @@ from __future__ import annotations
 
 import collections
 import math
+import re
 
 import numpy as np
 import torch
 
 ALIGN = 4  # fp32 elements (16 bytes)
+FLAG_TRAINABLE, FLAG_DECAY = 1, 2   # ROD_OPT_TRAINABLE / ROD_OPT_DECAY (include/rod.h)
+
+_DECAY_RE = re.compile(r'.*/(weights|kernel|weight_\d+)$')
+
+
+def default_decay(name: str) -> bool:
+    """Weight decay applies to conv / deconv / fully-connected weights (`.../weights`,
+    `.../kernel`, `.../weight_<i>`): what slim's MobileNet scope regularises.  Depthwise filters
+    (`depthwise_weights`), BatchNorm `gamma` / `beta` and `biases` / `bias` are left alone."""
+    return bool(_DECAY_RE.match(name))
 
 
 def trunc_normal(rng: np.random.Generator, shape, std: float) -> np.ndarray:
@@ -53,6 +64,7 @@ class ParamStore:
         self.offsets = {}
         self.device = None
         self.version = 0          # bumped whenever parameter values change (SGD step, load)
+        self.trainable_version = 0  # bumped by set_trainable (the optimiser's group flags follow it)
         self._prep = {}           # (name, mode, dtype) -> [prepped tensor, version, entry]
         self._prep_tables = {}    # dtype -> (device table, n, total) or None when stale
 
@@ -139,6 +151,22 @@ class ParamStore:
         """requires_grad per parameter name (train.py:160-166 trainable-var filtering)."""
         for name, p in self.params.items():
             p.requires_grad_(bool(predicate(name)))
+        self.trainable_version += 1
+
+    def group_flags(self, decay=None):
+        """Host uint8 [numel / ALIGN]: the flags of rod_sgd_momentum / rod_grad_sqnorm, one per
+        group of ALIGN elements (no group straddles two parameters).  Bit 0: the parameter
+        requires grad; bit 1: `decay(name)` (default_decay when None).  The padding after a
+        parameter whose size is no multiple of ALIGN shares its last group and its flags (the
+        padding's parameter, gradient and momentum elements are all zero, and stay zero under
+        the update); a group of padding alone cannot occur."""
+        decay = default_decay if decay is None else decay
+        flags = np.zeros(self.numel // ALIGN, dtype=np.uint8)
+        for name, p in self.params.items():
+            o, n = self.offsets[name]
+            bits = (FLAG_TRAINABLE if p.requires_grad else 0) | (FLAG_DECAY if decay(name) else 0)
+            flags[o // ALIGN:(o + n + ALIGN - 1) // ALIGN] = bits
+        return flags
 
     def trainable_count(self):
         return int(sum(p.numel() for p in self.params.values() if p.requires_grad))

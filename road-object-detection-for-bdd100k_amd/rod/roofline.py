@@ -206,6 +206,12 @@ def cost(name, a):
     if name == "rod_sgd_clip":
         n = a[2]
         return 12 * n, 3 * n                 # read param, read grad, write param (fp32)
+    if name == "rod_sgd_momentum":           # read p, g, m and the flags (1 byte / 4 elements), write p, m
+        n, mom = a[4], a[2] is not None
+        return (20 if mom else 12) * n + n // 4, 9 * n
+    if name == "rod_grad_sqnorm":            # read g and the flags
+        n = a[2]
+        return 4 * n + n // 4, 2 * n
     if name == "rod_conv_weight_prep_batch":
         total, dt = a[2], a[3]
         return (4 + _ES[dt]) * total, 0

@@ -3,7 +3,8 @@
 
   normalise -> corner->centre -> anchor matching (per image, batched on the GPU) ->
   network forward -> refine loss (+ det/clf loss in ALL) -> backward -> [DP all-reduce]
-  -> SGD with clip-by-value.
+  -> SGD with clip-by-value (or, opted in, momentum SGD with weight decay, norm clipping and a
+  learning-rate schedule: net_tools.optimizer).
 
 Data-parallel: one process per GPU, the per-image batch sharded across ranks; the
 flat gradient buffer is all-reduced (sum) over RCCL and losses are normalised by the
@@ -32,7 +33,8 @@ class Trainer:
                  learning_rate=1e-3, device='cuda', fix_refine=True, seed=0, world_size=1, reducer=None,
                  deconv_method=config.deconv_method.LEARN_HALF, merge_method=config.merge_method.ADD,
                  sync_bn=False, backbone_name='mobilenet_v2',
-                 process_backbone_method=config.process_backbone_method.NONE):
+                 process_backbone_method=config.process_backbone_method.NONE, momentum=0.0, nesterov=False,
+                 weight_decay=0.0, clip_norm=None, warmup_steps=0, fix_learning_rate=True):
         self.img_size = tuple(img_size)
         self.batch_size = batch_size          # per-rank batch
         self.world_size = world_size
@@ -54,7 +56,11 @@ class Trainer:
             import re
             pat = re.compile(r'^((?!(backbone|refine)).)*$')   # train.py:160-163
             store.set_trainable(lambda n: bool(pat.match(n)))
-        self.opt = net_tools.optimizer(store, batch_size * world_size, learning_rate)
+        # after set_trainable: the optimiser's group flags are built from requires_grad.  With every
+        # new option at its default this is the reference's plain SGD (one rod_sgd_clip launch)
+        self.opt = net_tools.optimizer(store, batch_size * world_size, learning_rate,
+                                       fix_learning_rate=fix_learning_rate, momentum=momentum, nesterov=nesterov,
+                                       weight_decay=weight_decay, clip_norm=clip_norm, warmup_steps=warmup_steps)
         self.reducer = reducer
         if reducer is not None and hasattr(reducer, 'attach'):
             reducer.attach(store)  # buckets over the trainable parameters (rod.ddp)
@@ -154,6 +160,7 @@ class Trainer:
                 graphs.pop(next(iter(graphs)))   # its graph and pool are freed with it
             static = tuple(t.clone() for t in new)
             self.net.store.build_prep_tables()   # host -> device set-up stays outside the capture
+            self.opt.refresh()                   # so does the device-side rate (the capture only reads it)
             g = torch.cuda.CUDAGraph()
             torch.cuda.synchronize()
             st = self.net.store
@@ -174,6 +181,8 @@ class Trainer:
         for a, b in zip(static, new):
             if a.data_ptr() != b.data_ptr():
                 a.copy_(b)
+        # the captured update reads its rate from device memory: this step's value, ahead of the replay
+        self.opt.refresh()
         g.replay()
         if mode == 'split':
             self.reducer(self.net.store.flat_grad)   # every bucket, back to back, then SGD

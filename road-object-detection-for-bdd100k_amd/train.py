@@ -8,7 +8,13 @@ hard-codes REFINE at train.py:130), --img_height/--img_width (config.img_size), 
 (fp32 like the reference's DTYPE, or bf16), --dataset_dir, --seed.  Data parallel when
 launched with several ranks (RCCL all-reduce of the flat gradient, global-batch loss
 normalisation; --batch_size is then per GPU).  Checkpoints are torch files holding the
-slim-named variables and global_step.
+slim-named variables and global_step (and, with --momentum, the momentum of every variable).
+
+Optimiser: by default the reference's (plain SGD, clip by value +-5, constant rate).  Opt in to
+--momentum / --nesterov, --weight_decay (conv / fc weights only), --clip_norm (global gradient
+norm), --warmup_steps (linear) and --fix_learning_rate=False (the 0.97 staircase the reference
+only logs becomes the applied rate); any of them selects the momentum-SGD kernel, under
+--hip_graph too.  The summary record's `lr` is the rate the step applied.
 """
 import argparse
 import json
@@ -71,19 +77,31 @@ def parse(argv=None):
                     help='replay the training step as a HIP graph (Trainer.step_graphed, bit-identical to the '
                          'eager step; dropout steps run eager).  Data parallel over RCCL: the whole step, its '
                          'collectives included (the library\'s communicator; gradient buckets on a side stream)')
+    # optimiser additions (all neutral by default: the reference's plain SGD step, bit for bit)
+    ap.add_argument('--momentum', type=float, default=0.0, help='SGD momentum (0 = none)')
+    ap.add_argument('--nesterov', type=str2bool, default=False, help='Nesterov momentum (needs --momentum > 0)')
+    ap.add_argument('--weight_decay', type=float, default=0.0,
+                    help='L2 weight decay on conv / fc weights (not depthwise filters, BatchNorm or biases), '
+                         'added to the clipped gradient')
+    ap.add_argument('--clip_norm', type=float, default=None,
+                    help='clip the gradient to this global L2 norm (before the clip by value)')
+    ap.add_argument('--warmup_steps', type=int, default=0, help='linear learning-rate warm-up over this many steps')
+    ap.add_argument('--fix_learning_rate', type=str2bool, default=True,
+                    help='False: apply the exponential staircase decay (0.97 every 20000 / batch_size steps) '
+                         'that the reference only logs')
     return ap.parse_args(argv)
 
 
-def load_ckpt(store, path, names_regex=None):
+def load_ckpt(store, path, names_regex=None, optimizer=None):
     """saver.restore (train.py:188, 282) / restore_saver of backbone.+|refine.+ (155-158, 191-193):
     a torch checkpoint written by this CLI or a TF-1.x tensor bundle of the reference."""
     from rod.checkpoint import load_variables
-    return load_variables(store, path, names_regex=names_regex)
+    return load_variables(store, path, names_regex=names_regex, optimizer=optimizer)
 
 
-def save_ckpt(store, path, step, fmt='torch'):
+def save_ckpt(store, path, step, fmt='torch', optimizer=None):
     from rod.checkpoint import save_variables
-    save_variables(store, path, step, fmt)
+    save_variables(store, path, step, fmt, optimizer=optimizer)
 
 
 def _loss_copy(losses, world):
@@ -138,7 +156,7 @@ class StepLog(object):
                 self.avg_t = 0.
         if self.summ is not None and F.summary_every_n_steps is not None and \
                 current_step % F.summary_every_n_steps == F.summary_every_n_steps - 1:
-            rec = {'step': current_step, 'loss': vals, 'lr': self.trainer.opt.decayed_lr(current_step)}
+            rec = {'step': current_step, 'loss': vals, 'lr': self.trainer.opt.summary_lr(current_step)}
             self.summ.write(json.dumps(rec) + '\n')
             self.summ.flush()
 
@@ -171,20 +189,21 @@ def main(argv=None):
     trainer = Trainer(config.img_size, F.batch_size, dtype=dtype, train_range=tr_range, learning_rate=F.learning_rate,
                       device=dev, fix_refine=F.fix_refine, seed=F.seed, world_size=world,
                       reducer=make_reducer(world, rank) if world > 1 else None, backbone_name=F.backbone_name,
-                      sync_bn=F.sync_bn)
+                      sync_bn=F.sync_bn, momentum=F.momentum, nesterov=F.nesterov, weight_decay=F.weight_decay,
+                      clip_norm=F.clip_norm, warmup_steps=F.warmup_steps, fix_learning_rate=F.fix_learning_rate)
     store = trainer.net.store
     logger.info('Total trainable parameters:%s' % str(store.trainable_count()))
     step0 = 0
     if tr_range is config.train_range.ALL:
         if F.checkpoint_all is not None:
-            step0 = load_ckpt(store, F.checkpoint_all)
+            step0 = load_ckpt(store, F.checkpoint_all, optimizer=trainer.opt)
             logger.info('Load checkpoint for all net success...')
         if F.checkpoint_refine is not None:
-            load_ckpt(store, F.checkpoint_refine, names_regex=r'backbone.+|refine.+')
+            load_ckpt(store, F.checkpoint_refine, names_regex=r'backbone.+|refine.+', optimizer=trainer.opt)
             logger.info('Load checkpoint for refine net success...')
     else:
         if F.checkpoint_refine is not None:
-            step0 = load_ckpt(store, F.checkpoint_refine)
+            step0 = load_ckpt(store, F.checkpoint_refine, optimizer=trainer.opt)
             logger.info('Load checkpoint success...')
         else:
             logger.info('TF variables init success...')
@@ -213,7 +232,8 @@ def main(argv=None):
         if F.save_every_n_steps is not None and current_step % F.save_every_n_steps == F.save_every_n_steps - 1 \
                 and rank == 0:
             logger.info('Saving model...')
-            save_ckpt(store, os.path.join(F.train_dir, F.backbone_name + '.model'), current_step + 1, F.save_format)
+            save_ckpt(store, os.path.join(F.train_dir, F.backbone_name + '.model'), current_step + 1, F.save_format,
+                      optimizer=trainer.opt)
             logger.info('Save model sucess...')
         if pending is not None:
             vals = _loss_values(pending[1])   # waits for the previous step only

@@ -194,23 +194,132 @@ class optimizer(object):
 
     The exponential decay the reference builds is only logged (net_tools.py:638-641,
     quirk 1 in SURVEY); `decayed_lr(step)` reproduces that logged value.
+
+    That is the default, one rod_sgd_clip launch (`entry == 'rod_sgd_clip'`).  Any of
+    momentum / nesterov / weight_decay / clip_norm / warmup_steps / fix_learning_rate=False
+    selects rod_sgd_momentum (formula and order in include/rod.h):
+
+        d = g * scale          scale = min(1, clip_norm / |g|) from rod_grad_sqnorm (clip_norm given)
+        d = clip(d, +-clip)    clip None: off
+        d = d + wd * p         where `decay(name)` (rod.params.default_decay: conv / fc weights)
+        m = mu * m + d ;  u = nesterov ? d + mu * m : m ;  p = p - lr * u
+
+    on the variables that require grad (store.group_flags; frozen ones are not touched).  The
+    applied rate is `applied_lr(step)`: `learning_rate`, or with fix_learning_rate=False the
+    staircase decayed_lr(step), times a linear warm-up min(1, (step + 1) / warmup_steps).  It
+    lives in device memory (`hyper[0]`; `hyper[1]` is the norm-clip scale): a captured step
+    reads the value the host last wrote, and the host writes it (refresh(), outside any capture,
+    on the step's stream ahead of the step) only when it changes.
     """
 
-    def __init__(self, store, batch_szie, learning_rate=1e-3, fix_learning_rate=True, clip=5.0):
+    def __init__(self, store, batch_szie, learning_rate=1e-3, fix_learning_rate=True, clip=5.0, momentum=0.0,
+                 nesterov=False, weight_decay=0.0, clip_norm=None, warmup_steps=0, decay=None):
         self.store = store
         self.lr = float(learning_rate)
         self.batch_size = batch_szie
-        self.fix = fix_learning_rate
+        self.fix = bool(fix_learning_rate)
         self.clip = clip
         self.global_step = 0
+        self.momentum = float(momentum)
+        self.nesterov = bool(nesterov)
+        self.weight_decay = float(weight_decay)
+        self.clip_norm = None if clip_norm is None else float(clip_norm)
+        self.warmup_steps = int(warmup_steps)
+        self.decay = decay
+        if self.momentum < 0 or self.weight_decay < 0 or self.warmup_steps < 0:
+            raise ValueError('momentum, weight_decay and warmup_steps must be >= 0')
+        if self.nesterov and self.momentum == 0:
+            raise ValueError('nesterov needs momentum > 0')
+        if self.clip_norm is not None and not self.clip_norm > 0:
+            raise ValueError('clip_norm must be > 0')
+        self.entry = 'rod_sgd_clip' if (self.momentum == 0 and not self.nesterov and self.weight_decay == 0 and
+                                        self.clip_norm is None and self.warmup_steps == 0 and self.fix) \
+            else 'rod_sgd_momentum'
+        self.mom = self.flags = self.hyper = self._ws = None
+        self._dev_lr = self._flags_version = None
+        if self.entry == 'rod_sgd_momentum':
+            dev = store.flat.device
+            # momentum 0: m = d is never read back, so no state buffer (same result as m = 0)
+            self.mom = torch.zeros_like(store.flat) if self.momentum != 0 else None
+            self.flags = torch.zeros(store.numel // 4, dtype=torch.uint8, device=dev)
+            self.hyper = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)   # [lr, scale]
+            if self.clip_norm is not None and dev.type == 'cuda':
+                self._ws = ops.grad_sqnorm_workspace(dev)
+            self.refresh()
 
     def decayed_lr(self, step=None):
         step = self.global_step if step is None else step
         return self.lr * 0.97 ** (step // (20000 / self.batch_size))
 
+    def applied_lr(self, step=None):
+        """The rate the update of step `step` (default: the next one) multiplies by."""
+        step = self.global_step if step is None else step
+        lr = self.lr if self.fix else self.decayed_lr(step)
+        if self.warmup_steps > 0:
+            lr = lr * min(1.0, (step + 1) / self.warmup_steps)
+        return lr
+
+    def summary_lr(self, step):
+        """The `lr` of train.py's summary record: the rate step `step` applied.  The default
+        optimiser keeps writing the reference's logged-only decay (quirk 1), as before."""
+        return self.decayed_lr(step) if self.entry == 'rod_sgd_clip' else self.applied_lr(step)
+
+    def refresh(self):
+        """Bring the device-side rate (and the group flags, after store.set_trainable) up to date
+        for the next step.  Host -> device writes, issued on the current stream only when a value
+        changed; never legal inside a graph capture, so step_graphed calls this before a capture
+        and before every replay."""
+        if self.entry == 'rod_sgd_clip':
+            return
+        lr = self.applied_lr()
+        stale_flags = self._flags_version != self.store.trainable_version
+        if lr == self._dev_lr and not stale_flags:
+            return
+        if self.hyper.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('optimizer.refresh() inside a graph capture: the rate or the trainable set '
+                               'changed since the last refresh; call refresh() before capturing')
+        if stale_flags:
+            self.flags.copy_(torch.from_numpy(self.store.group_flags(self.decay)))
+            self._flags_version = self.store.trainable_version
+        if lr != self._dev_lr:
+            self.hyper[:1].fill_(lr)
+            self._dev_lr = lr
+
+    def state_dict(self):
+        """{variable name: momentum} (host copies); empty without a momentum buffer."""
+        if self.mom is None:
+            return {}
+        return {n: self.mom[o:o + k].view(self.store.params[n].shape).detach().cpu().clone()
+                for n, (o, k) in self.store.offsets.items()}
+
+    def load_state_dict(self, sd, names_regex=None):
+        """Momentum of every variable (matching names_regex) from `sd`; zero where `sd` has none
+        (a checkpoint without optimiser state).  Ignored without a momentum buffer."""
+        if self.mom is None:
+            return
+        import re
+        pat = re.compile(names_regex) if names_regex else None
+        with torch.no_grad():
+            for n, (o, k) in self.store.offsets.items():
+                if pat is not None and not pat.match(n):
+                    continue
+                self.mom[o:-(-(o + k) // 4) * 4].zero_()      # the variable and its alignment padding
+                if n in sd:
+                    self.mom[o:o + k].copy_(torch.as_tensor(sd[n], dtype=torch.float32).reshape(-1))
+
     def step(self):
-        ops.sgd_clip_(self.store.flat, self.store.flat_grad, self.lr, self.clip)
-        self.store.version += 1   # derived weight layouts are refreshed (one batched launch) on next use
+        st = self.store
+        if self.entry == 'rod_sgd_clip':
+            ops.sgd_clip_(st.flat, st.flat_grad, self.lr, self.clip)
+        else:
+            self.refresh()
+            scale = None
+            if self.clip_norm is not None:
+                scale = self.hyper[1:2]
+                ops.grad_sqnorm_(st.flat_grad, self.flags, self.clip_norm, scale, self._ws)
+            ops.sgd_momentum_(st.flat, st.flat_grad, self.mom, self.flags, self.hyper[0:1], scale, self.momentum,
+                              self.weight_decay, float('inf') if self.clip is None else self.clip, self.nesterov)
+        st.version += 1   # derived weight layouts are refreshed (one batched launch) on next use
         self.global_step += 1
 
 
