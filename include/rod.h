@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ROD_ABI_VERSION 24
+#define ROD_ABI_VERSION 25
 #define ROD_EINVAL (-1)
 
 enum { ROD_F32 = 0, ROD_BF16 = 1, ROD_I32 = 2 /* collectives only (ABI 19) */ };
@@ -657,6 +657,31 @@ size_t rod_select_topk_nms_workspace(int B, int A, int K);
 int rod_select_topk_nms(const float* probs, const float* boxes, int B, int A, int K,
                         float select_threshold, int top_k, int keep_top_k, float nms_threshold,
                         float* out_scores, float* out_boxes, void* workspace, void* stream);
+
+/* Soft-NMS (Bodla et al., ICCV 2017; ABI 25; opt-in, the reference has none).  Same inputs,
+ * outputs, limits (top_k, keep_top_k <= 1024, B <= 65535), workspace query
+ * (rod_select_topk_nms_workspace) and front ends as rod_select_topk_nms; only the greedy stage
+ * differs.  For every image and class 1..K-1, independently:
+ *   candidates  s = p * (p >= select_threshold), boxes masked the same way; the
+ *               m = min(top_k, A) best in score order (desc, ties -> lower anchor index); a
+ *               candidate's position is its index in this order; working score w_i = s_i.
+ *   loop        until keep_top_k entries are emitted: pick the live candidate with the largest w
+ *               (ties -> lower position); stop if none is live or the pick fails
+ *               w > 0 && w >= min_score; emit (w, masked box), mark the pick dead, and for
+ *               every live j with iou = IoU(box_pick, box_j) (the hard entry's IoU):
+ *                 method 1 (linear)    if (iou > nms_threshold) w_j = w_j * (1.0f - iou);
+ *                 method 2 (gaussian)  t = iou * iou; t = t / sigma; w_j = w_j * exp(-t);
+ *               (gaussian ignores nms_threshold).  Every operation is one fp32 operation, no
+ *               contraction; exp is the correctly rounded (float)exp((double)x).
+ *   output      out_scores holds the RESCORED values, out_boxes the boxes, both in emission
+ *               order (scores non-increasing), zero-padded to keep_top_k.
+ * method must be 1 or 2; sigma > 0 and finite when method == 2; min_score >= 0 and finite
+ * (checked before any HIP call).  No host synchronisation, no allocation: capturable. */
+enum { ROD_SOFTNMS_LINEAR = 1, ROD_SOFTNMS_GAUSSIAN = 2 };
+int rod_select_topk_softnms(const float* probs, const float* boxes, int B, int A, int K,
+                            float select_threshold, int top_k, int keep_top_k, float nms_threshold,
+                            int method, float sigma, float min_score, float* out_scores,
+                            float* out_boxes, void* workspace, void* stream);
 
 /* ------------------------------------------------ optimiser (A14)
  * Plain SGD with clip by value (net_tools.py:645-651):

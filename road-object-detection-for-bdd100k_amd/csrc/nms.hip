@@ -20,6 +20,8 @@
 //  * direct (any threshold): per (image, class) an exact in-workgroup 4 x 8-bit radix select
 //    on the (non-negative) f32 score bits read column-wise from probs; candidates compacted in
 //    index order (ties resolved by index), then bitonic-sorted by (score desc, index asc).
+// rod_select_topk_softnms runs the same two front ends (the kernels are templates) and replaces
+// only the greedy stage, by soft_nms_greedy below.
 // Compiled with -ffp-contract=off.
 #include <math.h>
 
@@ -85,10 +87,84 @@ __device__ __forceinline__ float tf_iou(const float* bi, const float* bj) {
   return inter / (area_i + area_j - inter);
 }
 
+// ------------------------------------------------------------------- Soft-NMS greedy stage
+// (rod_select_topk_softnms; semantics in include/rod.h).  Replaces the greedy loop of both
+// kernels below when they are instantiated with SOFT: thread `tid` owns candidate position
+// `tid` (m <= NMS_T) and keeps its working score w in a register; its box stays in bx[tid],
+// which the loop never writes, so the picked box is a broadcast LDS read.  Each iteration is
+// one argmax over the 64-bit key (bits of w) << 32 | (NMS_T - 1 - position): w >= 0, so the
+// unsigned order of the bits is the order of the values and the larger key among equal scores
+// is the lower position; a dead candidate has key 0.  The reduction is __shfl_xor inside the
+// wave, then the 16 wave maxima through wred (two words per key, two buffers alternating by
+// iteration: a wave that runs ahead into iteration i+1 writes the other buffer than the one a
+// slower wave still reads for iteration i, so ONE barrier per iteration orders both).  Every
+// thread derives the same pick from the same LDS words: the exits are workgroup-uniform.
+// On entry sc[] holds the candidates' scores by position (already synchronised); on return
+// sc[j] / kept_idx[j] hold the j-th emitted (rescored) score / its position, j < the returned
+// count, and a barrier has made them visible.
+enum { SOFT_LINEAR = 1, SOFT_GAUSSIAN = 2 };
+struct SoftArgs {
+  int method;
+  float sigma, min_score;
+};
+
+__device__ __forceinline__ int soft_nms_greedy(int m, int keep_k, float nms_thr, SoftArgs sa, const float (*bx)[4],
+                                               float* sc, int* kept_idx, unsigned* wred) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  // a candidate of score 0 (below the select threshold: only the direct front end lists them) can
+  // never be emitted, so it starts dead — as if absent, which is what the candidate lists give
+  float w = tid < m ? sc[tid] : 0.f;
+  bool live = w > 0.f;
+  float mine[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) mine[q] = live ? bx[tid][q] : 0.f;
+  int kept = 0;
+  for (; kept < keep_k; ++kept) {
+    unsigned long long best = live ? ((unsigned long long)__float_as_uint(w) << 32) | (unsigned)(NMS_T - 1 - tid) : 0ull;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long other = __shfl_xor(best, o, 64);
+      best = other > best ? other : best;
+    }
+    unsigned* buf = wred + (kept & 1) * (2 * (NMS_T / 64));
+    if (lane == 0) {
+      buf[2 * wv] = (unsigned)best;
+      buf[2 * wv + 1] = (unsigned)(best >> 32);
+    }
+    __syncthreads();  // also orders every thread's read of sc[tid] before the first sc[0] store
+    best = 0ull;
+#pragma unroll
+    for (int q = 0; q < NMS_T / 64; ++q) {
+      const unsigned long long v = ((unsigned long long)buf[2 * q + 1] << 32) | buf[2 * q];
+      best = v > best ? v : best;
+    }
+    const float wp = __uint_as_float((unsigned)(best >> 32));
+    if (!(wp > 0.f && wp >= sa.min_score)) break;  // no live candidate has key 0 -> wp == 0
+    const int pick = NMS_T - 1 - (int)(best & 0xFFFFFFFFull);
+    if (tid == pick) {
+      sc[kept] = w;
+      kept_idx[kept] = pick;
+      live = false;
+    } else if (live) {
+      const float iou = tf_iou(bx[pick], mine);
+      if (sa.method == SOFT_LINEAR) {
+        if (iou > nms_thr) w = w * (1.0f - iou);
+      } else {
+        float t = iou * iou;
+        t = t / sa.sigma;
+        w = w * exp_cr(-t);
+      }
+    }
+  }
+  __syncthreads();
+  return kept;
+}
+
+template <bool SOFT>
 __global__ void __launch_bounds__(NMS_T) select_topk_nms_kernel(const float* __restrict__ probs,
                                                                  const float* __restrict__ boxes, int A, int K,
                                                                  float sel_thr, int top_k, int keep_k, float nms_thr,
-                                                                 float* __restrict__ out_scores,
+                                                                 SoftArgs sa, float* __restrict__ out_scores,
                                                                  float* __restrict__ out_boxes) {
   __shared__ unsigned hist[256];
   __shared__ unsigned sh[4];
@@ -189,24 +265,28 @@ __global__ void __launch_bounds__(NMS_T) select_topk_nms_kernel(const float* __r
     dead[tid] = 0;
   }
   __syncthreads();
-  // 5) greedy NMS in sorted order
+  // 5) greedy NMS in sorted order (SOFT: rescoring loop; hist is free by now)
   int kept = 0;
-  for (int i = 0; i < n && kept < keep_k; ++i) {
-    if (dead[i]) continue;  // uniform: dead[] only changes between barriers
-    if (tid == 0) kept_idx[kept] = i;
-    ++kept;
-    for (int j = i + 1 + tid; j < n; j += NMS_T)
-      if (!dead[j] && tf_iou(bx[i], bx[j]) > nms_thr) dead[j] = 1;
+  if constexpr (SOFT) {
+    kept = soft_nms_greedy(n, keep_k, nms_thr, sa, bx, sc, kept_idx, hist);
+  } else {
+    for (int i = 0; i < n && kept < keep_k; ++i) {
+      if (dead[i]) continue;  // uniform: dead[] only changes between barriers
+      if (tid == 0) kept_idx[kept] = i;
+      ++kept;
+      for (int j = i + 1 + tid; j < n; j += NMS_T)
+        if (!dead[j] && tf_iou(bx[i], bx[j]) > nms_thr) dead[j] = 1;
+      __syncthreads();
+    }
     __syncthreads();
   }
-  __syncthreads();
   // 6) write kept entries and zero padding
   float* os = out_scores + ((long)b * (K - 1) + (c - 1)) * keep_k;
   float* ob = out_boxes + ((long)b * (K - 1) + (c - 1)) * keep_k * 4;
   for (int j = tid; j < keep_k; j += NMS_T) {
     if (j < kept) {
       const int i = kept_idx[j];
-      os[j] = sc[i];
+      os[j] = SOFT ? sc[j] : sc[i];
 #pragma unroll
       for (int q = 0; q < 4; ++q) ob[j * 4 + q] = bx[i][q];
     } else {
@@ -292,10 +372,11 @@ __device__ void lds_bitonic(unsigned long long* key, int P) {
   }
 }
 
+template <bool SOFT>
 __global__ void __launch_bounds__(NMS_T) nms_select_kernel(const float* __restrict__ probs,
                                                            const float* __restrict__ boxes, int A, int K,
                                                            float sel_thr, int top_k, int keep_k, float nms_thr,
-                                                           const unsigned* __restrict__ counts,
+                                                           SoftArgs sa, const unsigned* __restrict__ counts,
                                                            const unsigned long long* __restrict__ keys,
                                                            float* __restrict__ out_scores,
                                                            float* __restrict__ out_boxes) {
@@ -377,27 +458,50 @@ __global__ void __launch_bounds__(NMS_T) nms_select_kernel(const float* __restri
   }
   __syncthreads();
   int kept = 0;
-  for (int i = 0; i < m && kept < keep_k; ++i) {
-    if (dead[i]) continue;  // uniform: dead[] only changes between barriers
-    if (tid == 0) kept_idx[kept] = i;
-    ++kept;
-    for (int j = i + 1 + tid; j < m; j += NMS_T)
-      if (!dead[j] && tf_iou(bx[i], bx[j]) > nms_thr) dead[j] = 1;
+  if constexpr (SOFT) {  // hist is free by now
+    kept = soft_nms_greedy(m, keep_k, nms_thr, sa, bx, sc, kept_idx, hist);
+  } else {
+    for (int i = 0; i < m && kept < keep_k; ++i) {
+      if (dead[i]) continue;  // uniform: dead[] only changes between barriers
+      if (tid == 0) kept_idx[kept] = i;
+      ++kept;
+      for (int j = i + 1 + tid; j < m; j += NMS_T)
+        if (!dead[j] && tf_iou(bx[i], bx[j]) > nms_thr) dead[j] = 1;
+      __syncthreads();
+    }
     __syncthreads();
   }
-  __syncthreads();
   float* os = out_scores + ((long)b * C + (c - 1)) * keep_k;
   float* ob = out_boxes + ((long)b * C + (c - 1)) * keep_k * 4;
   for (int j = tid; j < keep_k; j += NMS_T) {
     const bool kk = j < kept;
     const int i = kk ? kept_idx[j] : 0;
-    os[j] = kk ? sc[i] : 0.f;
+    os[j] = kk ? sc[SOFT ? j : i] : 0.f;
 #pragma unroll
     for (int q = 0; q < 4; ++q) ob[j * 4 + q] = kk ? bx[i][q] : 0.f;
   }
 }
 
 static size_t nms_counts_bytes(int B, int K) { return ((size_t)B * (K - 1) * sizeof(unsigned) + 255) / 256 * 256; }
+
+// both entries: the candidate-list front end when a workspace is given, the direct one otherwise
+template <bool SOFT>
+static void nms_launch(const float* probs, const float* boxes, int B, int A, int K, float select_threshold, int top_k,
+                       int keep_top_k, float nms_threshold, SoftArgs sa, float* out_scores, float* out_boxes,
+                       void* workspace, hipStream_t s) {
+  if (workspace && select_threshold > 0.f && K - 1 <= NMS_MAXC) {
+    unsigned* counts = (unsigned*)workspace;
+    unsigned long long* keys = (unsigned long long*)((char*)workspace + nms_counts_bytes(B, K));
+    hipLaunchKernelGGL(nms_zero_kernel, dim3(cdiv((long)B * (K - 1), 256)), dim3(256), 0, s, counts, B * (K - 1));
+    hipLaunchKernelGGL(nms_compact_kernel, dim3(cdiv(A, NMS_CT), B), dim3(256), 0, s, probs, A, K, select_threshold,
+                       counts, keys);
+    hipLaunchKernelGGL(nms_select_kernel<SOFT>, dim3(K - 1, B), dim3(NMS_T), 0, s, probs, boxes, A, K,
+                       select_threshold, top_k, keep_top_k, nms_threshold, sa, counts, keys, out_scores, out_boxes);
+  } else {
+    hipLaunchKernelGGL(select_topk_nms_kernel<SOFT>, dim3(K - 1, B), dim3(NMS_T), 0, s, probs, boxes, A, K,
+                       select_threshold, top_k, keep_top_k, nms_threshold, sa, out_scores, out_boxes);
+  }
+}
 
 }  // namespace rod
 
@@ -417,20 +521,27 @@ int rod_select_topk_nms(const float* probs, const float* boxes, int B, int A, in
   ROD_CHECK_ARG(top_k > 0 && top_k <= NMS_T, "rod_select_topk_nms: top_k must be in [1, %d]", NMS_T);
   ROD_CHECK_ARG(keep_top_k > 0 && keep_top_k <= NMS_T, "rod_select_topk_nms: keep_top_k must be in [1, %d]", NMS_T);
   ROD_CHECK_ARG(B <= 65535, "rod_select_topk_nms: B too large");
-  hipStream_t s = ROD_STREAM(stream);
-  if (workspace && select_threshold > 0.f && K - 1 <= NMS_MAXC) {
-    unsigned* counts = (unsigned*)workspace;
-    unsigned long long* keys = (unsigned long long*)((char*)workspace + nms_counts_bytes(B, K));
-    hipLaunchKernelGGL(nms_zero_kernel, dim3(cdiv((long)B * (K - 1), 256)), dim3(256), 0, s, counts, B * (K - 1));
-    hipLaunchKernelGGL(nms_compact_kernel, dim3(cdiv(A, NMS_CT), B), dim3(256), 0, s, probs, A, K, select_threshold,
-                       counts, keys);
-    hipLaunchKernelGGL(nms_select_kernel, dim3(K - 1, B), dim3(NMS_T), 0, s, probs, boxes, A, K, select_threshold,
-                       top_k, keep_top_k, nms_threshold, counts, keys, out_scores, out_boxes);
-  } else {
-    hipLaunchKernelGGL(select_topk_nms_kernel, dim3(K - 1, B), dim3(NMS_T), 0, s, probs, boxes, A, K,
-                       select_threshold, top_k, keep_top_k, nms_threshold, out_scores, out_boxes);
-  }
+  nms_launch<false>(probs, boxes, B, A, K, select_threshold, top_k, keep_top_k, nms_threshold, SoftArgs{0, 0.f, 0.f},
+                    out_scores, out_boxes, workspace, ROD_STREAM(stream));
   return check_launch("rod_select_topk_nms");
+}
+
+int rod_select_topk_softnms(const float* probs, const float* boxes, int B, int A, int K, float select_threshold,
+                            int top_k, int keep_top_k, float nms_threshold, int method, float sigma, float min_score,
+                            float* out_scores, float* out_boxes, void* workspace, void* stream) {
+  ROD_CHECK_ARG(B > 0 && A > 0 && K > 1, "rod_select_topk_softnms: bad shape");
+  ROD_CHECK_ARG(top_k > 0 && top_k <= NMS_T, "rod_select_topk_softnms: top_k must be in [1, %d]", NMS_T);
+  ROD_CHECK_ARG(keep_top_k > 0 && keep_top_k <= NMS_T, "rod_select_topk_softnms: keep_top_k must be in [1, %d]",
+                NMS_T);
+  ROD_CHECK_ARG(B <= 65535, "rod_select_topk_softnms: B too large");
+  ROD_CHECK_ARG(method == SOFT_LINEAR || method == SOFT_GAUSSIAN,
+                "rod_select_topk_softnms: method must be 1 (linear) or 2 (gaussian), got %d", method);
+  ROD_CHECK_ARG(method != SOFT_GAUSSIAN || (sigma > 0.f && isfinite(sigma)),
+                "rod_select_topk_softnms: sigma must be > 0 and finite");
+  ROD_CHECK_ARG(min_score >= 0.f && isfinite(min_score), "rod_select_topk_softnms: min_score must be >= 0 and finite");
+  nms_launch<true>(probs, boxes, B, A, K, select_threshold, top_k, keep_top_k, nms_threshold,
+                   SoftArgs{method, sigma, min_score}, out_scores, out_boxes, workspace, ROD_STREAM(stream));
+  return check_launch("rod_select_topk_softnms");
 }
 
 }  // extern "C"

@@ -40,6 +40,12 @@ def parse(argv=None):
     ap.add_argument('--matching_threshold', type=float, default=0.5)
     ap.add_argument('--gpu_memory_fraction', type=float, default=0.8)
     # additions
+    ap.add_argument('--nms_method', default='hard', choices=['hard', 'linear', 'gaussian'],
+                    help="'hard': the reference's greedy NMS; 'linear' / 'gaussian': Soft-NMS (overlapped "
+                         'detections are rescored, not dropped; AP is computed on the rescored scores)')
+    ap.add_argument('--soft_nms_sigma', type=float, default=0.5, help='gaussian Soft-NMS: exp(-iou^2 / sigma)')
+    ap.add_argument('--soft_nms_min_score', type=float, default=0.001,
+                    help='Soft-NMS stops emitting below this rescored score')
     ap.add_argument('--num_images', type=int, default=3000, help='evaluate.py:219 hard-codes 3000')
     ap.add_argument('--img_height', type=int, default=config.img_size[0])
     ap.add_argument('--img_width', type=int, default=config.img_size[1])
@@ -113,7 +119,9 @@ def main(argv=None):
             boxes = net_tools.decode_all_layers(anchors_all, refine_out, det_out, to_corner=True)
             rscores, rbboxes = net_tools.detected_bboxes(probs, boxes, select_threshold=F.select_threshold,
                                                          nms_threshold=F.nms_threshold, top_k=F.select_top_k,
-                                                         keep_top_k=F.keep_top_k)
+                                                         keep_top_k=F.keep_top_k, nms_method=F.nms_method,
+                                                         soft_nms_sigma=F.soft_nms_sigma,
+                                                         soft_nms_min_score=F.soft_nms_min_score)
             rs = {c: v.cpu().numpy() for c, v in rscores.items()}
             rb = {c: v.cpu().numpy() for c, v in rbboxes.items()}
             gl, gb, gcount = glabels.cpu().numpy(), gboxes.cpu().numpy(), gn.cpu().numpy()

@@ -41,6 +41,12 @@ def parse(argv=None):
     ap.add_argument('--nms_threshold', type=float, default=0.4)
     ap.add_argument('--top_k', type=int, default=400)
     ap.add_argument('--keep_top_k', type=int, default=200)
+    ap.add_argument('--nms_method', default='hard', choices=['hard', 'linear', 'gaussian'],
+                    help="'hard': the reference's greedy NMS; 'linear' / 'gaussian': Soft-NMS (overlapped "
+                         'detections are rescored, not dropped; the scores reported are the rescored ones)')
+    ap.add_argument('--soft_nms_sigma', type=float, default=0.5, help='gaussian Soft-NMS: exp(-iou^2 / sigma)')
+    ap.add_argument('--soft_nms_min_score', type=float, default=0.001,
+                    help='Soft-NMS stops emitting below this rescored score')
     ap.add_argument('--img_height', type=int, default=config.img_size[0])
     ap.add_argument('--img_width', type=int, default=config.img_size[1])
     ap.add_argument('--dtype', default='fp32', choices=['fp32', 'bf16'])
@@ -59,9 +65,12 @@ class Predictor(object):
     """Forward + decode + per-class NMS; reused by bench (inference FPS)."""
 
     def __init__(self, img_size, device, dtype=torch.float32, checkpoint=None, select_threshold=0.1,
-                 nms_threshold=0.4, top_k=400, keep_top_k=200, seed=0, backbone_name='mobilenet_v2'):
+                 nms_threshold=0.4, top_k=400, keep_top_k=200, seed=0, backbone_name='mobilenet_v2',
+                 nms_method='hard', soft_nms_sigma=0.5, soft_nms_min_score=0.001):
         from nets.catch_net import CatchNet
         from utils import net_tools
+        if nms_method not in ('hard', 'linear', 'gaussian'):
+            raise ValueError("nms_method must be 'hard', 'linear' or 'gaussian', got %r" % (nms_method,))
         config.img_size = tuple(img_size)
         self.config_dict = {'process_backbone_method': config.process_backbone_method.NONE,
                             'deconv_method': config.deconv_method.LEARN_HALF,
@@ -77,7 +86,8 @@ class Predictor(object):
         self.keep_intermediates = False   # tests: keep (logits, probs, boxes) of the last call
         self.last = None
         self.kw = dict(select_threshold=select_threshold, nms_threshold=nms_threshold, top_k=top_k,
-                       keep_top_k=keep_top_k)
+                       keep_top_k=keep_top_k, nms_method=nms_method, soft_nms_sigma=soft_nms_sigma,
+                       soft_nms_min_score=soft_nms_min_score)
         # the whole forward + decode + NMS is captured once per input shape as a HIP graph and
         # replayed (no per-kernel host dispatch); re-captured when the parameters change
         self.use_graph = device.type == 'cuda' and os.environ.get('ROD_PREDICT_GRAPH', '1') != '0'
@@ -98,7 +108,10 @@ class Predictor(object):
                          ops.levels_concat(refine_out, 4), ops.levels_concat(det_out, 4))
         kw = self.kw                                                                        # 136-137
         thr = 0.0 if kw['select_threshold'] is None else kw['select_threshold']
-        return ops.select_topk_nms(probs, boxes, thr, kw['top_k'], kw['keep_top_k'], kw['nms_threshold'])
+        if kw['nms_method'] == 'hard':
+            return ops.select_topk_nms(probs, boxes, thr, kw['top_k'], kw['keep_top_k'], kw['nms_threshold'])
+        return ops.select_topk_soft_nms(probs, boxes, thr, kw['top_k'], kw['keep_top_k'], kw['nms_threshold'],
+                                        kw['nms_method'], kw['soft_nms_sigma'], kw['soft_nms_min_score'])
 
     @torch.no_grad()
     def __call__(self, img_u8):
@@ -106,7 +119,8 @@ class Predictor(object):
         if not self.use_graph or self.keep_intermediates:
             scores, boxes = self._forward(img_u8)
         else:
-            key = (tuple(img_u8.shape), img_u8.dtype, self.net.store.version)
+            key = (tuple(img_u8.shape), img_u8.dtype, self.net.store.version, self.kw['nms_method'],
+                   self.kw['soft_nms_sigma'], self.kw['soft_nms_min_score'])
             if self._graph is None or self._graph[0] != key:
                 self._graph = None
                 static_in = img_u8.clone()
@@ -168,7 +182,8 @@ def main(argv=None):
                                     % F.checkpoint_all)
         logger.warning('--synthetic: checkpoint %r not found, predicting with random weights', F.checkpoint_all)
     pred = Predictor((F.img_height, F.img_width), dev, dtype, ckpt, F.select_threshold, F.nms_threshold, F.top_k,
-                     F.keep_top_k, backbone_name=F.backbone_name)
+                     F.keep_top_k, backbone_name=F.backbone_name, nms_method=F.nms_method,
+                     soft_nms_sigma=F.soft_nms_sigma, soft_nms_min_score=F.soft_nms_min_score)
     logger.info('Building data pileline, using dataset---%s' % 'bdd100k_train')
     source = make_source(F.dataset_dir, F.batch_size, config.img_size, dev, synthetic=F.synthetic, dtype=dtype,
                          num_readers=F.num_readers)

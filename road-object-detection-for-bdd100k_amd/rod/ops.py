@@ -1875,6 +1875,27 @@ def select_topk_nms(probs, boxes, select_threshold, top_k, keep_top_k, nms_thres
     return scores, bxs
 
 
+SOFT_NMS_METHODS = {'linear': 1, 'gaussian': 2}   # ROD_SOFTNMS_* (include/rod.h)
+
+
+def select_topk_soft_nms(probs, boxes, select_threshold, top_k, keep_top_k, nms_threshold, method, sigma=0.5,
+                         min_score=0.001, compact=True):
+    """rod_select_topk_softnms: select_topk_nms with the greedy stage replaced by Soft-NMS
+    (method 'linear' or 'gaussian'; semantics in include/rod.h).  The scores returned are the
+    rescored ones, in emission order.  compact as in select_topk_nms."""
+    if method not in SOFT_NMS_METHODS:
+        raise ValueError("select_topk_soft_nms: method must be 'linear' or 'gaussian', got %r" % (method,))
+    B, A, K = probs.shape
+    dev = probs.device
+    scores = torch.empty((B, K - 1, keep_top_k), dtype=torch.float32, device=dev)
+    bxs = torch.empty((B, K - 1, keep_top_k, 4), dtype=torch.float32, device=dev)
+    ws = workspace(_abi.query("rod_select_topk_nms_workspace", B, A, K), dev) if compact else None
+    _abi.call("rod_select_topk_softnms", probs.contiguous(), boxes.contiguous(), B, A, K, float(select_threshold),
+              int(top_k), int(keep_top_k), float(nms_threshold), SOFT_NMS_METHODS[method], float(sigma),
+              float(min_score), scores, bxs, ws, stream())
+    return scores, bxs
+
+
 # ----------------------------------------------------------------------------- VGG-16 ops (F3)
 # slim.conv2d with activation_fn and no normaliser (vgg_arg_scope: relu, nets/backbone/vgg.py:58):
 # the conv's output y is left as an owned Pending with an identity BatchNorm (mean 0, rstd 1,

@@ -229,6 +229,11 @@ def cost(name, a):
     if name == "rod_select_topk_nms":
         B, A, K = a[2], a[3], a[4]
         return B * A * (K * 4 + 16), 0
+    if name == "rod_select_topk_softnms":
+        # same traffic; the rescoring loop: <= keep_top_k picks x min(top_k, A) candidates per
+        # (image, class), ~25 flops per IoU + rescore (the double-precision exp not counted)
+        B, A, K, top_k, keep = a[2], a[3], a[4], a[6], a[7]
+        return B * A * (K * 4 + 16), 25 * B * (K - 1) * keep * min(top_k, A)
     if name == "rod_det_targets":
         B, A, dt = a[13], a[14], a[15]
         return B * A * (4 * _ES[dt] + 16 + 16 + 4 + 4 + 16 + 4 + 4 + 4), 40 * B * A

@@ -416,18 +416,28 @@ def class_probabilities(clf_out):
 
 
 def detected_bboxes(predictions, localisations, select_threshold=None, nms_threshold=0.5, clipping_bbox=None,
-                    top_k=800, keep_top_k=200):
+                    top_k=800, keep_top_k=200, nms_method='hard', soft_nms_sigma=0.5, soft_nms_min_score=0.001):
     """Per-class select -> top_k -> NMS -> pad (net_tools.py:739-758) in one kernel.
 
     predictions: [B, A_total, K] probabilities (or the per-layer list of them);
     localisations: [B, A_total, 4] corner boxes (or the per-layer list).
+    nms_method: 'hard' (the reference's greedy NMS) or, opt-in, Soft-NMS 'linear' / 'gaussian'
+    (rod_select_topk_softnms: overlapped candidates are rescored instead of dropped, the
+    returned scores are the rescored ones, emission stops below soft_nms_min_score; 'gaussian'
+    uses soft_nms_sigma and ignores nms_threshold).
     Returns dicts {c: scores [B, keep_top_k]}, {c: boxes [B, keep_top_k, 4]} for c = 1..K-1."""
+    if nms_method not in ('hard', 'linear', 'gaussian'):
+        raise ValueError("nms_method must be 'hard', 'linear' or 'gaussian', got %r" % (nms_method,))
     if isinstance(predictions, (list, tuple)):
         predictions = ops.levels_concat([p.float() for p in predictions], config.total_obj_n)
     if isinstance(localisations, (list, tuple)):
         localisations = ops.levels_concat([l.float() for l in localisations], 4)
     thr = 0.0 if select_threshold is None else select_threshold
-    scores, boxes = ops.select_topk_nms(predictions, localisations, thr, top_k, keep_top_k, nms_threshold)
+    if nms_method == 'hard':
+        scores, boxes = ops.select_topk_nms(predictions, localisations, thr, top_k, keep_top_k, nms_threshold)
+    else:
+        scores, boxes = ops.select_topk_soft_nms(predictions, localisations, thr, top_k, keep_top_k, nms_threshold,
+                                                 nms_method, soft_nms_sigma, soft_nms_min_score)
     if clipping_bbox is not None:
         raise NotImplementedError('clipping_bbox is never used by the reference CLIs (predict.py:136)')
     K = predictions.shape[-1]

@@ -78,11 +78,13 @@ def bboxes_flip_left_right(bboxes):
     return np.stack([b[..., 0], 1 - b[..., 3], b[..., 2], 1 - b[..., 1]], -1)
 
 
-def _select_one_class(scores, bboxes, top_k, keep_top_k, nms_threshold):
+def _select_one_class(scores, bboxes, top_k, keep_top_k, nms_threshold, nms_method='hard', soft_nms_sigma=0.5,
+                      soft_nms_min_score=0.001):
     """rod_select_topk_nms on ONE class's [B, N] scores and [B, N, 4] boxes (device tensors):
     the scores become column 1 of a [B, N, 2] table (column 0, the background, is ignored by
     the kernel), select threshold 0 keeps every row (scores are probabilities, >= 0), so the
-    kernel runs top-k (descending, ties to the lower index) and greedy NMS only."""
+    kernel runs top-k (descending, ties to the lower index) and greedy NMS only.  nms_method
+    'linear' / 'gaussian': rod_select_topk_softnms in its place (net_tools.detected_bboxes)."""
     import torch
     from rod import ops
     s = torch.as_tensor(scores)
@@ -92,8 +94,14 @@ def _select_one_class(scores, bboxes, top_k, keep_top_k, nms_threshold):
     B, N = s.shape
     probs = torch.zeros((B, N, 2), dtype=torch.float32, device=s.device)
     probs[..., 1] = s.float()
-    out_s, out_b = ops.select_topk_nms(probs, b.float().contiguous(), 0.0, top_k, keep_top_k, nms_threshold,
-                                       compact=False)
+    if nms_method == 'hard':
+        out_s, out_b = ops.select_topk_nms(probs, b.float().contiguous(), 0.0, top_k, keep_top_k, nms_threshold,
+                                           compact=False)
+    elif nms_method in ('linear', 'gaussian'):
+        out_s, out_b = ops.select_topk_soft_nms(probs, b.float().contiguous(), 0.0, top_k, keep_top_k, nms_threshold,
+                                                nms_method, soft_nms_sigma, soft_nms_min_score, compact=False)
+    else:
+        raise ValueError("nms_method must be 'hard', 'linear' or 'gaussian', got %r" % (nms_method,))
     return out_s[:, 0], out_b[:, 0]
 
 
@@ -112,15 +120,21 @@ def bboxes_sort(scores, bboxes, top_k=400, scope=None):
     return _select_one_class(scores, bboxes, top_k, top_k, float('inf'))
 
 
-def bboxes_nms_batch(scores, bboxes, nms_threshold=0.5, keep_top_k=200, scope=None):
+def bboxes_nms_batch(scores, bboxes, nms_threshold=0.5, keep_top_k=200, scope=None, nms_method='hard',
+                     soft_nms_sigma=0.5, soft_nms_min_score=0.001):
     """bboxes.py:192-232: tf.image.non_max_suppression per image (greedy in score order, a box
     is dropped when its IoU with a kept one is > nms_threshold), the kept scores / boxes in
     score order, zero-padded to keep_top_k — [B, keep_top_k], [B, keep_top_k, 4]; dicts per
-    class as in the reference.  N <= 1024 candidates per image (the output of bboxes_sort)."""
+    class as in the reference.  N <= 1024 candidates per image (the output of bboxes_sort).
+    nms_method 'linear' / 'gaussian' (opt-in, not in the reference): Soft-NMS, the scores
+    returned are the rescored ones (net_tools.detected_bboxes)."""
     if isinstance(scores, dict) or isinstance(bboxes, dict):
-        out = {c: bboxes_nms_batch(scores[c], bboxes[c], nms_threshold, keep_top_k) for c in scores}
+        out = {c: bboxes_nms_batch(scores[c], bboxes[c], nms_threshold, keep_top_k, nms_method=nms_method,
+                                   soft_nms_sigma=soft_nms_sigma, soft_nms_min_score=soft_nms_min_score)
+               for c in scores}
         return {c: v[0] for c, v in out.items()}, {c: v[1] for c, v in out.items()}
-    return _select_one_class(scores, bboxes, scores.shape[-1], keep_top_k, nms_threshold)
+    return _select_one_class(scores, bboxes, scores.shape[-1], keep_top_k, nms_threshold, nms_method,
+                             soft_nms_sigma, soft_nms_min_score)
 
 
 def bboxes_matching(label, scores, bboxes, glabels, gbboxes, gdifficults, matching_threshold=0.5, scope=None):
