@@ -932,15 +932,12 @@ static void apply_launch(bool vec, const void* x, const float* mean, const float
                          int act, hipStream_t s) {
   const int V = vec ? Vec16<T>::N : 1;
   const int blocks = const_channel_blocks(C / V, apply_threads(M * (C / V)), apply_target(M * (C / V)));
-#define LA(VE, RE)                                                                                            \
-  hipLaunchKernelGGL((bn_apply_kernel<T, VE, RE>), dim3(blocks), dim3(256), 0, s, (const T*)x, mean, rstd, gamma, \
-                     beta, (const T*)res, (T*)y, M, C, ldx, ldr, ldy, act)
-  if (vec) {
-    if (res) LA(true, true); else LA(true, false);
-  } else {
-    if (res) LA(false, true); else LA(false, false);
-  }
-#undef LA
+  sel_bool(vec, [&](auto VE) {
+    sel_bool(res != nullptr, [&](auto RE) {
+      hipLaunchKernelGGL((bn_apply_kernel<T, VE, RE>), dim3(blocks), dim3(256), 0, s, (const T*)x, mean, rstd, gamma,
+                         beta, (const T*)res, (T*)y, M, C, ldx, ldr, ldy, act);
+    });
+  });
 }
 
 template <typename T>

@@ -1254,22 +1254,32 @@ static int dw_pack(const void* a, const void* b, int C, int cap) {
   if (C % 4 == 0 && al(4 * sizeof(T))) return 4;
   return 1;
 }
+// the register-strip launches' (stride, channels per thread) from the stride and dw_pack's 8 / 4 / 1:
+// f(S, V) with V = the 16-byte pack for 8 (4 for fp32, so no 8-wide fp32 form is built)
+template <typename T, typename F>
+static void dw_select(int stride, int pk, F&& f) {
+  const int v = pk == 8 ? Vec16<T>::N : pk == 4 ? 4 : 1;
+  sel_int<1, 2>(stride == 1 ? 1 : 2, [&](auto S) { sel_int<Vec16<T>::N, 4, 1>(v, [&](auto V) { f(S, V); }); });
+}
+// the BatchNorm-prologue form a depthwise kernel is built for (its PACT): -1 none, ReLU6
+// inlined, DW_ACT_RT any other activation (read at run time)
+static int dw_pact(const BnPro* pro) { return !pro ? -1 : (pro->act == ROD_ACT_RELU6 ? ROD_ACT_RELU6 : DW_ACT_RT); }
+template <typename F>
+static void sel_pact(const BnPro* pro, F&& f) {
+  sel_int<ROD_ACT_RELU6, DW_ACT_RT, -1>(dw_pact(pro), f);
+}
 
 template <typename T, int S, int V>
 static void dw_fwd_launch(const void* x, const BnPro* pro, const float* w, void* y, float* parts, int N, int H, int W,
                           int C, int pt, int pl, int Ho, int Wo, hipStream_t s) {
   const dim3 grid = dw_fwd_grid(N, Ho, Wo, C, V);
   const BnPro pv = pro ? *pro : BnPro{};
-#define DWF(ST, PA)                                                                                              \
-  hipLaunchKernelGGL((dw3x3_fwd_kernel<T, S, V, ST, PA>), grid, dim3(256), 0, s, (const T*)x, w, (T*)y, H, W, C, pt, \
-                     pl, Ho, Wo, parts, pv)
-  const int pa = !pro ? -1 : (pro->act == ROD_ACT_RELU6 ? ROD_ACT_RELU6 : DW_ACT_RT);
-  if (parts) {
-    if (pa == ROD_ACT_RELU6) DWF(true, ROD_ACT_RELU6); else if (pa == DW_ACT_RT) DWF(true, DW_ACT_RT); else DWF(true, -1);
-  } else {
-    if (pa == ROD_ACT_RELU6) DWF(false, ROD_ACT_RELU6); else if (pa == DW_ACT_RT) DWF(false, DW_ACT_RT); else DWF(false, -1);
-  }
-#undef DWF
+  sel_bool(parts != nullptr, [&](auto ST) {
+    sel_pact(pro, [&](auto PA) {
+      hipLaunchKernelGGL((dw3x3_fwd_kernel<T, S, V, ST, PA>), grid, dim3(256), 0, s, (const T*)x, w, (T*)y, H, W, C,
+                         pt, pl, Ho, Wo, parts, pv);
+    });
+  });
 }
 // LDS-exchange forward: needs 16-byte packs (C % V == 0, 16-byte aligned x and y).
 template <typename T>
@@ -1289,27 +1299,18 @@ static long dw_fwd_lx_launch(const void* x, const BnPro* pro, const float* w, vo
   const DwTile t = dw_tile(N, Ho, Wo, C, S, V);
   const dim3 grid(t.coltiles * t.cgroups, t.strips, N);
   const BnPro pv = pro ? *pro : BnPro{};
-  const int pa = !pro ? -1 : (pro->act == ROD_ACT_RELU6 ? ROD_ACT_RELU6 : DW_ACT_RT);
-#define DWL(S_, PA, ST)                                                                                           \
-  do {                                                                                                            \
-    if (sizeof(T) == 2 && V == 4)                                                                                 \
-      hipLaunchKernelGGL((dw3x3_fwd_lx_kernel<T, S_, PA, ST, 4>), grid, dim3(256), 0, s, (const T*)x, w, (T*)y, H, W, \
-                         C, pt, pl, Ho, Wo, t, parts, pv);                                                        \
-    else                                                                                                          \
-      hipLaunchKernelGGL((dw3x3_fwd_lx_kernel<T, S_, PA, ST>), grid, dim3(256), 0, s, (const T*)x, w, (T*)y, H, W,  \
-                         C, pt, pl, Ho, Wo, t, parts, pv);                                                        \
-  } while (0)
-#define DWL_PA(S_, ST)                    \
-  if (pa == ROD_ACT_RELU6) DWL(S_, ROD_ACT_RELU6, ST); \
-  else if (pa == DW_ACT_RT) DWL(S_, DW_ACT_RT, ST); \
-  else DWL(S_, -1, ST)
-  if (S == 1) {
-    if (parts) { DWL_PA(1, true); } else { DWL_PA(1, false); }
-  } else {
-    if (parts) { DWL_PA(2, true); } else { DWL_PA(2, false); }
-  }
-#undef DWL_PA
-#undef DWL
+  // the kernel's pack is the 16-byte one unless dw_fwd_v picked 4 channels for bf16
+  const int vk = sizeof(T) == 2 && V == 4 ? 4 : Vec16<T>::N;
+  sel_int<1, 2>(S == 1 ? 1 : 2, [&](auto S_) {
+    sel_pact(pro, [&](auto PA) {
+      sel_bool(parts != nullptr, [&](auto ST) {
+        sel_int<Vec16<T>::N, 4>(vk, [&](auto VK) {
+          hipLaunchKernelGGL((dw3x3_fwd_lx_kernel<T, S_, PA, ST, VK>), grid, dim3(256), 0, s, (const T*)x, w, (T*)y,
+                             H, W, C, pt, pl, Ho, Wo, t, parts, pv);
+        });
+      });
+    });
+  });
   return (long)N * t.strips * t.coltiles;
 }
 
@@ -1333,12 +1334,10 @@ static long dw_bwd_data_lx_launch(const void* dy, const float* w, void* dx, cons
   const DwTile t = dw_tile(N, H, W, C, 1, Vec16<T>::N);
   const dim3 grid(t.coltiles * t.cgroups, t.strips, N);
   const BnGred g = gr ? *gr : BnGred{};
-  if (gr)
-    hipLaunchKernelGGL((dw3x3_bwd_data_lx_kernel<T, true>), grid, dim3(256), 0, s, (const T*)dy, w, (T*)dx, Ho, Wo,
-                       C, 2 - pt, 2 - pl, H, W, t, g);
-  else
-    hipLaunchKernelGGL((dw3x3_bwd_data_lx_kernel<T, false>), grid, dim3(256), 0, s, (const T*)dy, w, (T*)dx, Ho, Wo,
-                       C, 2 - pt, 2 - pl, H, W, t, g);
+  sel_bool(gr != nullptr, [&](auto GRED) {
+    hipLaunchKernelGGL((dw3x3_bwd_data_lx_kernel<T, GRED>), grid, dim3(256), 0, s, (const T*)dy, w, (T*)dx, Ho, Wo, C,
+                       2 - pt, 2 - pl, H, W, t, g);
+  });
   return (long)N * t.strips * t.coltiles;
 }
 
@@ -1348,54 +1347,48 @@ static void dw_bwd_data_launch(const void* dy, const float* w, void* dx, int N, 
   bool s2k;
   const dim3 grid = dw_bwd_data_grid(N, H, W, C, S, pt, pl, V, &s2k);
   const BnGred g = gr ? *gr : BnGred{};
-  if (s2k) {
-    const int Bc = (W - 1 + pl) / 2 + 1;
-    if (gr)
-      hipLaunchKernelGGL((dw3x3_bwd_data_s2_kernel<T, V, true>), grid, dim3(256), 0, s, (const T*)dy, w, (T*)dx, H, W,
+  const int Bc = (W - 1 + pl) / 2 + 1;
+  sel_bool(gr != nullptr, [&](auto GRED) {
+    if (s2k)
+      hipLaunchKernelGGL((dw3x3_bwd_data_s2_kernel<T, V, GRED>), grid, dim3(256), 0, s, (const T*)dy, w, (T*)dx, H, W,
                          C, pt, pl, Ho, Wo, Bc, g);
     else
-      hipLaunchKernelGGL((dw3x3_bwd_data_s2_kernel<T, V, false>), grid, dim3(256), 0, s, (const T*)dy, w, (T*)dx, H,
-                         W, C, pt, pl, Ho, Wo, Bc, g);
-    return;
-  }
-  if (gr)
-    hipLaunchKernelGGL((dw3x3_bwd_data_kernel<T, S, V, true>), grid, dim3(256), 0, s, (const T*)dy, w, (T*)dx, H, W,
-                       C, pt, pl, Ho, Wo, g);
-  else
-    hipLaunchKernelGGL((dw3x3_bwd_data_kernel<T, S, V, false>), grid, dim3(256), 0, s, (const T*)dy, w, (T*)dx, H, W,
-                       C, pt, pl, Ho, Wo, g);
+      hipLaunchKernelGGL((dw3x3_bwd_data_kernel<T, S, V, GRED>), grid, dim3(256), 0, s, (const T*)dy, w, (T*)dx, H, W,
+                         C, pt, pl, Ho, Wo, g);
+  });
 }
 template <typename T, int S, int V>
 static void dw_bwd_filter_launch(const void* x, const BnPro* pro, const void* dy, float* dw, float* slab, int N, int H,
                                  int W, int C, int pt, int pl, int Ho, int Wo, hipStream_t s) {
   DwFilterPlan p = dw_filter_plan(N, Ho, Wo, C, V, (int)sizeof(T));
   const BnPro pv = pro ? *pro : BnPro{};
-#define DWW(PA)                                                                                                   \
-  hipLaunchKernelGGL((dw3x3_bwd_filter_kernel<T, S, V, PA>), dim3(p.gx, p.gy), dim3(256), 256 * V * sizeof(float), \
-                     s, (const T*)x, (const T*)dy, slab, N, H, W, C, pt, pl, Ho, Wo, p.RB, p.spi, pv)
-  const int pa = !pro ? -1 : (pro->act == ROD_ACT_RELU6 ? ROD_ACT_RELU6 : DW_ACT_RT);
-  if (pa == ROD_ACT_RELU6) DWW(ROD_ACT_RELU6); else if (pa == DW_ACT_RT) DWW(DW_ACT_RT); else DWW(-1);
-#undef DWW
+  sel_pact(pro, [&](auto PA) {
+    hipLaunchKernelGGL((dw3x3_bwd_filter_kernel<T, S, V, PA>), dim3(p.gx, p.gy), dim3(256), 256 * V * sizeof(float),
+                       s, (const T*)x, (const T*)dy, slab, N, H, W, C, pt, pl, Ho, Wo, p.RB, p.spi, pv);
+  });
   slab_sum(slab, dw, (int)p.parts(), 9L * C, s);
+}
+// filter gradient on the LDS-exchange kernel (16-byte packs); GP: its fused form, which takes dz
+// for dy and applies the BatchNorm backward of gd on the way (rod_dw3x3_bwd_filter_bn)
+template <typename T, bool GP>
+static void dw_bwdw_lx_launch(const void* x, const BnPro* pro, const void* dy, float* dw, float* slab,
+                              const DwGrad& gd, int N, int H, int W, int C, int stride, int pt, int pl, int Ho, int Wo,
+                              hipStream_t s) {
+  const DwTile t = dw_tile(N, Ho, Wo, C, stride, Vec16<T>::N);
+  const dim3 grid(t.coltiles * t.cgroups, t.strips, N);
+  const BnPro pv = pro ? *pro : BnPro{};
+  sel_int<1, 2>(stride == 1 ? 1 : 2, [&](auto S) {
+    sel_pact(pro, [&](auto PA) {
+      hipLaunchKernelGGL((dw3x3_bwdw_lx_kernel<T, S, PA, GP>), grid, dim3(256), 0, s, (const T*)x, (const T*)dy, slab,
+                         H, W, C, pt, pl, Ho, Wo, t, pv, gd);
+    });
+  });
+  slab_sum(slab, dw, (int)((long)N * t.strips * t.coltiles), 9L * C, s);
 }
 
 }  // namespace rod
 
 using namespace rod;
-
-// dispatch on stride and channel pack; defines the launch for T_ (pack from the pointers)
-#define DW_SELECT(FN, T_, PK, ...)                                            \
-  do {                                                                        \
-    if (stride == 1) {                                                        \
-      if ((PK) == 8) FN<T_, 1, (sizeof(T_) == 2 ? 8 : 4)>(__VA_ARGS__);      \
-      else if ((PK) == 4) FN<T_, 1, 4>(__VA_ARGS__);                          \
-      else FN<T_, 1, 1>(__VA_ARGS__);                                         \
-    } else {                                                                  \
-      if ((PK) == 8) FN<T_, 2, (sizeof(T_) == 2 ? 8 : 4)>(__VA_ARGS__);      \
-      else if ((PK) == 4) FN<T_, 2, 4>(__VA_ARGS__);                          \
-      else FN<T_, 2, 1>(__VA_ARGS__);                                         \
-    }                                                                         \
-  } while (0)
 
 extern "C" {
 
@@ -1431,16 +1424,13 @@ int rod_dw3x3_fwd(const void* x, const float* pro_mean, const float* pro_rstd, c
     // the fused statistics write one part per block; when that is not the count the caller
     // sized the slab for (misaligned pointers, legacy switch), a separate pass writes them
     const bool fuse = stat_parts && (long)g.x * g.y * g.z == nparts;
-    DW_SELECT(dw_fwd_launch, T, pk, x, pp, w, y, fuse ? stat_parts : nullptr, N, H, W, C, pad_t, pad_l, Ho, Wo, s);
+    dw_select<T>(stride, pk, [&](auto S, auto VP) {
+      dw_fwd_launch<T, S, VP>(x, pp, w, y, fuse ? stat_parts : nullptr, N, H, W, C, pad_t, pad_l, Ho, Wo, s);
+    });
     if (stat_parts && !fuse)
       ::rod::stat_parts(sizeof(T) == 4 ? ROD_F32 : ROD_BF16, y, (long)N * Ho * Wo, C, C, stat_parts, nparts, s);
   };
-  if (dtype == ROD_F32) run(float{});
-  else if (dtype == ROD_BF16) run(bf16_t{});
-  else {
-    set_error("rod_dw3x3_fwd: bad dtype %d", dtype);
-    return ROD_EINVAL;
-  }
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_dw3x3_fwd: bad dtype %d", dtype);
   return check_launch("rod_dw3x3_fwd");
 }
 
@@ -1484,15 +1474,12 @@ int rod_dw3x3_bwd_data(const void* dy, const float* w, void* dx, const void* gre
     // 16-byte-aligned y too); otherwise a separate pass
     const bool fuse = gred_parts && (long)g.x * g.y * g.z == nparts && (((uintptr_t)gred_y) & 15) == 0;
     const BnGred* gp = fuse ? &gr : nullptr;
-    DW_SELECT(dw_bwd_data_launch, T, pk, dy, w, dx, N, H, W, C, pad_t, pad_l, Ho, Wo, gp, s);
+    dw_select<T>(stride, pk, [&](auto S, auto VP) {
+      dw_bwd_data_launch<T, S, VP>(dy, w, dx, N, H, W, C, pad_t, pad_l, Ho, Wo, gp, s);
+    });
     if (gred_parts && !fuse) ::rod::gred_parts(dtype, dx, gred_y, gr.p, (long)N * H * W, C, gred_parts, nparts, s);
   };
-  if (dtype == ROD_F32) run(float{});
-  else if (dtype == ROD_BF16) run(bf16_t{});
-  else {
-    set_error("rod_dw3x3_bwd_data: bad dtype %d", dtype);
-    return ROD_EINVAL;
-  }
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_dw3x3_bwd_data: bad dtype %d", dtype);
   return check_launch("rod_dw3x3_bwd_data");
 }
 
@@ -1517,37 +1504,17 @@ int rod_dw3x3_bwd_filter(const void* x, const float* pro_mean, const float* pro_
   float* slab = (float*)workspace;
   const BnPro pro{pro_mean, pro_rstd, pro_gamma, pro_beta, pro_act};
   const BnPro* pp = pro_mean ? &pro : nullptr;
-  auto lx = [&](auto tag) {  // LDS-exchange kernel (16-byte packs)
+  auto run = [&](auto tag) {
     typedef decltype(tag) T;
-    const DwTile t = dw_tile(N, Ho, Wo, C, stride, Vec16<T>::N);
-    const dim3 grid(t.coltiles * t.cgroups, t.strips, N);
-    const BnPro pv = pp ? *pp : BnPro{};
-    const int pa = !pp ? -1 : (pp->act == ROD_ACT_RELU6 ? ROD_ACT_RELU6 : DW_ACT_RT);
-#define DWW(S_, PA)                                                                                               \
-  hipLaunchKernelGGL((dw3x3_bwdw_lx_kernel<T, S_, PA>), grid, dim3(256), 0, s, (const T*)x, (const T*)dy, slab, H, W, \
-                     C, pad_t, pad_l, Ho, Wo, t, pv)
-    if (stride == 1) {
-      if (pa == ROD_ACT_RELU6) DWW(1, ROD_ACT_RELU6); else if (pa == DW_ACT_RT) DWW(1, DW_ACT_RT); else DWW(1, -1);
-    } else {
-      if (pa == ROD_ACT_RELU6) DWW(2, ROD_ACT_RELU6); else if (pa == DW_ACT_RT) DWW(2, DW_ACT_RT); else DWW(2, -1);
+    if (dw_lx_ok<T>(x, dy, C)) {
+      dw_bwdw_lx_launch<T, false>(x, pp, dy, dw, slab, DwGrad{}, N, H, W, C, stride, pad_t, pad_l, Ho, Wo, s);
+      return;
     }
-#undef DWW
-    slab_sum(slab, dw, (int)((long)N * t.strips * t.coltiles), 9L * C, s);
+    dw_select<T>(stride, dw_pack<T>(x, dy, C, 4), [&](auto S, auto VP) {
+      dw_bwd_filter_launch<T, S, VP>(x, pp, dy, dw, slab, N, H, W, C, pad_t, pad_l, Ho, Wo, s);
+    });
   };
-  if (dtype == ROD_F32 && dw_lx_ok<float>(x, dy, C)) {
-    lx(float{});
-  } else if (dtype == ROD_BF16 && dw_lx_ok<bf16_t>(x, dy, C)) {
-    lx(bf16_t{});
-  } else if (dtype == ROD_F32) {
-    const int pk = dw_pack<float>(x, dy, C, 4);
-    DW_SELECT(dw_bwd_filter_launch, float, pk, x, pp, dy, dw, slab, N, H, W, C, pad_t, pad_l, Ho, Wo, s);
-  } else if (dtype == ROD_BF16) {
-    const int pk = dw_pack<bf16_t>(x, dy, C, 4);
-    DW_SELECT(dw_bwd_filter_launch, bf16_t, pk, x, pp, dy, dw, slab, N, H, W, C, pad_t, pad_l, Ho, Wo, s);
-  } else {
-    set_error("rod_dw3x3_bwd_filter: bad dtype %d", dtype);
-    return ROD_EINVAL;
-  }
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_dw3x3_bwd_filter: bad dtype %d", dtype);
   return check_launch("rod_dw3x3_bwd_filter");
 }
 
@@ -1570,22 +1537,8 @@ int rod_dw3x3_bwd_filter_bn(const void* x, const float* pro_mean, const float* p
   const BnPro* pp = pro_mean ? &pro : nullptr;
   const DwGrad gd{y, bn_mean, bn_rstd, bn_gamma, bn_beta, coef, bn_act, dy};
   auto gp = [&](auto tag) {  // the fused kernel (LDS-exchange engine, 16-byte packs)
-    typedef decltype(tag) T;
-    const DwTile t = dw_tile(N, Ho, Wo, C, stride, Vec16<T>::N);
-    const dim3 grid(t.coltiles * t.cgroups, t.strips, N);
-    const BnPro pv = pp ? *pp : BnPro{};
-    const int pa = !pp ? -1 : (pp->act == ROD_ACT_RELU6 ? ROD_ACT_RELU6 : DW_ACT_RT);
-    float* slab = (float*)workspace;
-#define DWG(S_, PA)                                                                                                \
-  hipLaunchKernelGGL((dw3x3_bwdw_lx_kernel<T, S_, PA, true>), grid, dim3(256), 0, s, (const T*)x, (const T*)dz, slab, \
-                     H, W, C, pad_t, pad_l, Ho, Wo, t, pv, gd)
-    if (stride == 1) {
-      if (pa == ROD_ACT_RELU6) DWG(1, ROD_ACT_RELU6); else if (pa == DW_ACT_RT) DWG(1, DW_ACT_RT); else DWG(1, -1);
-    } else {
-      if (pa == ROD_ACT_RELU6) DWG(2, ROD_ACT_RELU6); else if (pa == DW_ACT_RT) DWG(2, DW_ACT_RT); else DWG(2, -1);
-    }
-#undef DWG
-    slab_sum(slab, dw, (int)((long)N * t.strips * t.coltiles), 9L * C, s);
+    dw_bwdw_lx_launch<decltype(tag), true>(x, pp, dz, dw, (float*)workspace, gd, N, H, W, C, stride, pad_t, pad_l, Ho,
+                                           Wo, s);
   };
   const bool al = ((((uintptr_t)y) | ((uintptr_t)dy)) & 15) == 0;
   if (dtype == ROD_BF16 && al && dw_lx_ok<bf16_t>(x, dz, C)) {
@@ -2742,105 +2695,73 @@ int rod_dw3x3_bwd_fused(const void* ye, const float* pro_mean, const float* pro_
   const dim3 grid(t.coltiles * t.cgroups, t.strips, N);
   const BnPro pv{pro_mean, pro_rstd, pro_gamma, pro_beta, pro_act};
   const DwBwdBn bd{bn_mean, bn_rstd, bn_gamma, bn_beta, coef, bn_act};
-  const int pa = !pro_mean ? -1 : (pro_act == ROD_ACT_RELU6 ? ROD_ACT_RELU6 : DW_ACT_RT);
   float* slab = (float*)workspace;
-  auto go = [&](auto tag) {
+  // A/B measurement switches, each read once; the defaults and what they measured:
+  //  * stride 1 runs the issue-lean kernel (fused2); ROD_DWF_V1=1 the first form (fused);
+  //  * both prefetch through a 3-step ring; ROD_DWF_RING=6 a 6-step one (3.27 vs 3.34 ms for the
+  //    first form over the step's bf16 shapes; with 2 channels it needs 131 VGPRs, 3 waves/SIMD);
+  //  * bf16 stride 1: 2 channels per thread in 512-thread blocks (122 VGPRs, 4 waves/SIMD: with
+  //    branch-free buffer I/O the ring's wait counts are exact); ROD_DWF_C2=0 the 4-channel form;
+  //  * bf16 stride 2: the packed kernel (s2p); ROD_DWF_S2P=0 the scalar one (s2), which fp32
+  //    always takes, with a ring of 2 steps for bf16 (238 VGPRs; 3 spill) and 1 for fp32;
+  //  * packed with a ReLU6 BN_d: 2 channels per thread in 512-thread blocks (116 VGPRs, 4 waves /
+  //    SIMD instead of 2 at 204: tools/dwfused_bench.py stride-2 shapes 1686 -> 1604 us, dx
+  //    bit-identical); ROD_DWF_S2P_V=4 the 4-channel form, ROD_DWF_S2P_D=3 a 3-step ring.
+  static const int ring = getenv("ROD_DWF_RING") && atoi(getenv("ROD_DWF_RING")) == 6 ? 6 : 3;
+  static const bool v1 = getenv("ROD_DWF_V1") && atoi(getenv("ROD_DWF_V1")) == 1;
+  static const bool c2 = !(getenv("ROD_DWF_C2") && atoi(getenv("ROD_DWF_C2")) == 0);
+  static const bool s2p = !(getenv("ROD_DWF_S2P") && atoi(getenv("ROD_DWF_S2P")) == 0);
+  static const bool s2p2 = !(getenv("ROD_DWF_S2P_V") && atoi(getenv("ROD_DWF_S2P_V")) == 4);
+  static const bool s2pd3 = getenv("ROD_DWF_S2P_D") && atoi(getenv("ROD_DWF_S2P_D")) == 3;
+  const int ba = bn_act == ROD_ACT_RELU6 ? ROD_ACT_RELU6 : DW_ACT_RT;   // BN_d's activation: inlined ReLU6 or run time
+  // PA: the input prologue's form; R: also sum BN_e's backward parts (needs the prologue)
+  auto go = [&](auto tag, auto PA, auto R) {
     typedef decltype(tag) T;
-    // 4-channel stride-1 forms: prefetch ring depth 3; ROD_DWF_RING=6 (measurement switch)
-    // measured 3.27 ms (3) vs 3.34 ms (6) for the first form over the step's bf16 shapes
-    static const int ring_env = getenv("ROD_DWF_RING") ? atoi(getenv("ROD_DWF_RING")) : 0;
-    const int ring = ring_env == 6 ? 6 : 3;
-    // stride 1: the issue-lean kernel; ROD_DWF_V1=1 (A/B switch) the first form
-    static const bool v1 = getenv("ROD_DWF_V1") && atoi(getenv("ROD_DWF_V1")) == 1;
-    // bf16 default: 2 channels per thread in 512-thread blocks (122 VGPRs, 4 waves/SIMD) with a
-    // 3-step ring: with branch-free buffer loads / stores the ring's wait counts are exact, and a
-    // 6-step ring needs 131 VGPRs (3 waves/SIMD; capped at 128 it spills).  ROD_DWF_C2=0 the
-    // 4-channel form, ROD_DWF_RING=6 the 6-step ring
-    static const bool v2 = !(getenv("ROD_DWF_C2") && atoi(getenv("ROD_DWF_C2")) == 0);
-    const int vring = ring_env == 6 ? 6 : 3;
-#define DWF1(PA, R, D)                                                                                               \
-  hipLaunchKernelGGL((dw3x3_bwd_fused_kernel<T, PA, R, D>), grid, dim3(256), 0, s, (const T*)ye, (const T*)dz,      \
-                     (const T*)yd, w, (T*)dx, slab, gparts, H, W, C, t, pv, bd)
-    // stride 2 ring (branch-free buffer I/O, exact wait counts): 2 steps for bf16 (238 VGPRs;
-    // 3 steps spill), 1 for fp32 (16-byte slots: 2 steps spill)
-    constexpr int D2 = sizeof(T) == 2 ? 2 : 1;
-    // bf16: the packed form (ROD_DWF_S2P=0: the scalar one)
-    static const bool s2p = !(getenv("ROD_DWF_S2P") && atoi(getenv("ROD_DWF_S2P")) == 0);
-    // packed stride-2 form with 2 channels a thread in 512-thread blocks (116 VGPRs: 4 waves /
-    // SIMD instead of 2 at 204): tools/dwfused_bench.py stride-2 shapes 1686 -> 1604 us, dx
-    // bit-identical.  ROD_DWF_S2P_V=4: the 4-channel form; ROD_DWF_S2P_D=3: a 3-step ring (A/B)
-    static const bool s2p2 = !(getenv("ROD_DWF_S2P_V") && atoi(getenv("ROD_DWF_S2P_V")) == 4);
-    static const bool s2pd3 = getenv("ROD_DWF_S2P_D") && atoi(getenv("ROD_DWF_S2P_D")) == 3;
-#define DWS2(PA, R)                                                                                                  \
-  do {                                                                                                              \
-    if constexpr (sizeof(T) == 2) {                                                                                 \
-      if (s2p && s2p2 && s2pd3 && bn_act == ROD_ACT_RELU6) {                                                        \
-        hipLaunchKernelGGL((dw3x3_bwd_fused_s2p_kernel<PA, R, ROD_ACT_RELU6, 3, 2>), grid, dim3(512), 0, s,         \
-                           (const bf16_t*)ye, (const bf16_t*)dz, (const bf16_t*)yd, w, (bf16_t*)dx, slab, gparts, H,  \
-                           W, C, pad_t, pad_l, Ho, Wo, t, pv, bd);                                                  \
-        break;                                                                                                      \
-      }                                                                                                             \
-      if (s2p && s2p2 && bn_act == ROD_ACT_RELU6) {                                                                 \
-        hipLaunchKernelGGL((dw3x3_bwd_fused_s2p_kernel<PA, R, ROD_ACT_RELU6, 2, 2>), grid, dim3(512), 0, s,         \
-                           (const bf16_t*)ye, (const bf16_t*)dz, (const bf16_t*)yd, w, (bf16_t*)dx, slab, gparts, H,  \
-                           W, C, pad_t, pad_l, Ho, Wo, t, pv, bd);                                                  \
-        break;                                                                                                      \
-      }                                                                                                             \
-      if (s2p && bn_act == ROD_ACT_RELU6) {                                                                         \
-        hipLaunchKernelGGL((dw3x3_bwd_fused_s2p_kernel<PA, R, ROD_ACT_RELU6>), grid, dim3(256), 0, s,               \
-                           (const bf16_t*)ye, (const bf16_t*)dz, (const bf16_t*)yd, w, (bf16_t*)dx, slab, gparts, H,  \
-                           W, C, pad_t, pad_l, Ho, Wo, t, pv, bd);                                                  \
-        break;                                                                                                      \
-      }                                                                                                             \
-      if (s2p) {                                                                                                    \
-        hipLaunchKernelGGL((dw3x3_bwd_fused_s2p_kernel<PA, R, DW_ACT_RT>), grid, dim3(256), 0, s, (const bf16_t*)ye,  \
-                           (const bf16_t*)dz, (const bf16_t*)yd, w, (bf16_t*)dx, slab, gparts, H, W, C, pad_t, pad_l, \
-                           Ho, Wo, t, pv, bd);                                                                      \
-        break;                                                                                                      \
-      }                                                                                                             \
-    }                                                                                                               \
-    hipLaunchKernelGGL((dw3x3_bwd_fused_s2_kernel<T, PA, R, D2>), grid, dim3(256), 0, s, (const T*)ye, (const T*)dz, \
-                       (const T*)yd, w, (T*)dx, slab, gparts, H, W, C, pad_t, pad_l, Ho, Wo, t, pv, bd);             \
-  } while (0)
-#define DWV2(PA, R, BA)                                                                                              \
-  do {                                                                                                              \
-    if constexpr (sizeof(T) == 2) {                                                                                 \
-      if (v2 && vring == 6)                                                                                         \
-        hipLaunchKernelGGL((dw3x3_bwd_fused2_kernel<T, PA, R, BA, 2, 6>), grid, dim3(512), 0, s, (const T*)ye,      \
-                           (const T*)dz, (const T*)yd, w, (T*)dx, slab, gparts, H, W, C, t, pv, bd);                \
-      else if (v2)                                                                                                  \
-        hipLaunchKernelGGL((dw3x3_bwd_fused2_kernel<T, PA, R, BA, 2>), grid, dim3(512), 0, s, (const T*)ye,         \
-                           (const T*)dz, (const T*)yd, w, (T*)dx, slab, gparts, H, W, C, t, pv, bd);                \
-      if (v2) break;                                                                                                \
-    }                                                                                                               \
-    if (ring == 6)                                                                                                  \
-      hipLaunchKernelGGL((dw3x3_bwd_fused2_kernel<T, PA, R, BA, 4, 6>), grid, dim3(256), 0, s, (const T*)ye,        \
-                         (const T*)dz, (const T*)yd, w, (T*)dx, slab, gparts, H, W, C, t, pv, bd);                  \
-    else                                                                                                            \
-      hipLaunchKernelGGL((dw3x3_bwd_fused2_kernel<T, PA, R, BA>), grid, dim3(256), 0, s, (const T*)ye, (const T*)dz, \
-                         (const T*)yd, w, (T*)dx, slab, gparts, H, W, C, t, pv, bd);                                \
-  } while (0)
-#define DWF2(PA, R)                                                                                                  \
-  do {                                                                                                              \
-    if (stride == 2) DWS2(PA, R);                                                                                   \
-    else if (!v1 && bn_act == ROD_ACT_RELU6) DWV2(PA, R, ROD_ACT_RELU6);                                            \
-    else if (!v1) DWV2(PA, R, DW_ACT_RT);                                                                           \
-    else if (ring == 3) DWF1(PA, R, 3);                                                                             \
-    else DWF1(PA, R, 6);                                                                                            \
-  } while (0)
-    if (pa == ROD_ACT_RELU6) {
-      if (gparts) DWF2(ROD_ACT_RELU6, true); else DWF2(ROD_ACT_RELU6, false);
-    } else if (pa == DW_ACT_RT) {
-      if (gparts) DWF2(DW_ACT_RT, true); else DWF2(DW_ACT_RT, false);
-    } else {
-      DWF2(-1, false);
+    constexpr bool BF = sizeof(T) == 2;
+    auto launch = [&](auto kern, int block, auto... tail) {
+      hipLaunchKernelGGL(kern, grid, dim3(block), 0, s, (const T*)ye, (const T*)dz, (const T*)yd, w, (T*)dx, slab,
+                         gparts, H, W, C, tail...);
+    };
+    if (stride == 2) {
+      if constexpr (BF) {
+        if (s2p && s2p2 && ba == ROD_ACT_RELU6) {
+          sel_int<2, 3>(s2pd3 ? 3 : 2, [&](auto D) {
+            launch(dw3x3_bwd_fused_s2p_kernel<PA, R, ROD_ACT_RELU6, D, 2>, 512, pad_t, pad_l, Ho, Wo, t, pv, bd);
+          });
+          return;
+        }
+        if (s2p) {
+          sel_int<ROD_ACT_RELU6, DW_ACT_RT>(ba, [&](auto BA) {
+            launch(dw3x3_bwd_fused_s2p_kernel<PA, R, BA, 2, 4>, 256, pad_t, pad_l, Ho, Wo, t, pv, bd);
+          });
+          return;
+        }
+      }
+      launch(dw3x3_bwd_fused_s2_kernel<T, PA, R, BF ? 2 : 1>, 256, pad_t, pad_l, Ho, Wo, t, pv, bd);
+      return;
     }
-#undef DWF2
-#undef DWV2
-#undef DWS2
-#undef DWF1
+    sel_int<3, 6>(ring, [&](auto D) {
+      if (v1) {
+        launch(dw3x3_bwd_fused_kernel<T, PA, R, D>, 256, t, pv, bd);
+        return;
+      }
+      sel_int<ROD_ACT_RELU6, DW_ACT_RT>(ba, [&](auto BA) {
+        if constexpr (BF) {
+          if (c2) {
+            launch(dw3x3_bwd_fused2_kernel<T, PA, R, BA, 2, D>, 512, t, pv, bd, DwPw{});
+            return;
+          }
+        }
+        launch(dw3x3_bwd_fused2_kernel<T, PA, R, BA, 4, D>, 256, t, pv, bd, DwPw{});
+      });
+    });
   };
-  if (dtype == ROD_BF16) go(bf16_t{}); else go(float{});
+  sel_dtype(dtype, [&](auto tag) {
+    sel_pact(pro_mean ? &pv : nullptr, [&](auto PA) {
+      if constexpr (PA == -1) go(tag, PA, std::false_type{});   // no prologue, no BN_e sums
+      else sel_bool(gparts != nullptr, [&](auto R) { go(tag, PA, R); });
+    });
+  });
   const int rc = check_launch("rod_dw3x3_bwd_fused");
   if (rc) return rc;
   slab_sum(slab, dw, (int)((long)N * t.strips * t.coltiles), 9L * C, s);
@@ -2880,12 +2801,11 @@ int rod_dw3x3_bwd_fused_pw(const void* ye, const float* pro_mean, const float* p
   const DwBwdBn bd{bn_mean, bn_rstd, bn_gamma, bn_beta, coef, bn_act};
   const DwPw pw{(const bf16_t*)dyp, (const bf16_t*)wt1, cout};
   float* slab = (float*)workspace;
-#define DWPW(R)                                                                                                     \
-  hipLaunchKernelGGL((dw3x3_bwd_fused2_kernel<bf16_t, ROD_ACT_RELU6, R, ROD_ACT_RELU6, 2, 3, true>), grid, dim3(512), \
-                     0, s, (const bf16_t*)ye, (const bf16_t*)nullptr, (const bf16_t*)yd, w, (bf16_t*)dx, slab, gparts,  \
-                     H, W, C, t, pv, bd, pw)
-  if (gparts) DWPW(true); else DWPW(false);
-#undef DWPW
+  sel_bool(gparts != nullptr, [&](auto R) {
+    hipLaunchKernelGGL((dw3x3_bwd_fused2_kernel<bf16_t, ROD_ACT_RELU6, R, ROD_ACT_RELU6, 2, 3, true>), grid,
+                       dim3(512), 0, s, (const bf16_t*)ye, (const bf16_t*)nullptr, (const bf16_t*)yd, w, (bf16_t*)dx,
+                       slab, gparts, H, W, C, t, pv, bd, pw);
+  });
   const int rc = check_launch("rod_dw3x3_bwd_fused_pw");
   if (rc) return rc;
   slab_sum(slab, dw, (int)((long)N * t.strips * t.coltiles), 9L * C, s);

@@ -747,40 +747,20 @@ int rod_dw3x3_fwd_rc(const void* x, const float* x_mean, const float* x_rstd, co
                    Ho, Wo};
   const dim3 grid(t.coltiles * t.cgroups, t.strips, N);
   hipStream_t s = ROD_STREAM(stream);
-#define RCN(S_, V_, CI_, ST_)                                                                                  \
-  do {                                                                                                         \
-    if (l.npt <= 2)                                                                                            \
-      hipLaunchKernelGGL((dw3x3_fwd_rc_kernel<S_, V_, CI_, ST_, 2>), grid, dim3(256), l.total, s, a, t, l.nct, \
-                         l.ldy);                                                                               \
-    else if (l.npt == 3)                                                                                       \
-      hipLaunchKernelGGL((dw3x3_fwd_rc_kernel<S_, V_, CI_, ST_, 3>), grid, dim3(256), l.total, s, a, t, l.nct, \
-                         l.ldy);                                                                               \
-    else                                                                                                       \
-      hipLaunchKernelGGL((dw3x3_fwd_rc_kernel<S_, V_, CI_, ST_, 4>), grid, dim3(256), l.total, s, a, t, l.nct, \
-                         l.ldy);                                                                               \
-  } while (0)
-#define RCK(S_, V_, CI_)                         \
-  do {                                           \
-    if (stat_parts) RCN(S_, V_, CI_, true);      \
-    else RCN(S_, V_, CI_, false);                \
-  } while (0)
-#define RCV(S_, CI_)                   \
-  do {                                 \
-    if (V == 8) RCK(S_, 8, CI_);       \
-    else RCK(S_, 4, CI_);              \
-  } while (0)
-#define RCC(S_)                                    \
-  do {                                             \
-    if (Cin == 16) RCV(S_, 16);                    \
-    else if (Cin == 24) RCV(S_, 24);               \
-    else RCV(S_, 32);                              \
-  } while (0)
-  if (stride == 1) RCC(1);
-  else RCC(2);
-#undef RCC
-#undef RCV
-#undef RCK
-#undef RCN
+  const int npt = l.npt <= 2 ? 2 : l.npt;   // pixel tiles the kernel is built for: 2, 3 or 4 (the plan: <= 4)
+  const bool hit = sel_int<1, 2>(stride, [&](auto S) {
+    return sel_int<4, 8>(V, [&](auto VP) {
+      return sel_int<16, 24, 32>(Cin, [&](auto CI) {
+        return sel_bool(stat_parts != nullptr, [&](auto ST) {
+          return sel_int<2, 3, 4>(npt, [&](auto NPT) {
+            hipLaunchKernelGGL((dw3x3_fwd_rc_kernel<S, VP, CI, ST, NPT>), grid, dim3(256), l.total, s, a, t, l.nct,
+                               l.ldy);
+          });
+        });
+      });
+    });
+  });
+  ROD_CHECK_ARG(hit, "rod_dw3x3_fwd_rc: no kernel for stride=%d V=%d Cin=%d npt=%d", stride, V, Cin, l.npt);
   return check_launch("rod_dw3x3_fwd_rc");
 }
 
@@ -835,25 +815,15 @@ int rod_dw3x3_bwd_fused_rc(const void* x, const float* x_mean, const float* x_rs
   const DwBwdBn bd{bn_mean, bn_rstd, bn_gamma, bn_beta, coef, bn_act};
   float* sl = (float*)workspace;
   hipStream_t s = ROD_STREAM(stream);
-#define RCB0(CI_, NC_)                                                                                          \
-  do {                                                                                                          \
-    (void)hipFuncSetAttribute((const void*)dw3x3_bwd_fused_rc_kernel<CI_, NC_>,                                \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
-    hipLaunchKernelGGL((dw3x3_bwd_fused_rc_kernel<CI_, NC_>), grid, dim3(512), lds, s, (const bf16_t*)x, xp,   \
-                       (const bf16_t*)wt0, (const bf16_t*)dz, (const bf16_t*)yd, w, (bf16_t*)dx, sl, gparts, H, W, C, \
-                       pad_t, pad_l, Ho, Wo, t, ep, bd);                                                       \
-  } while (0)
-#define RCB(CI_)                      \
-  do {                                \
-    if (nct <= 2) RCB0(CI_, 2);       \
-    else if (nct == 3) RCB0(CI_, 3);  \
-    else RCB0(CI_, 4);                \
-  } while (0)
-  if (Cin == 16) RCB(16);
-  else if (Cin == 24) RCB(24);
-  else RCB(32);
-#undef RCB
-#undef RCB0
+  const int nc = nct <= 2 ? 2 : nct;   // channel tiles the kernel is built for: 2, 3 or 4 (the plan: <= 4)
+  const bool hit = sel_int<16, 24, 32>(Cin, [&](auto CI) {
+    return sel_int<2, 3, 4>(nc, [&](auto NC) {
+      launch_lds(dw3x3_bwd_fused_rc_kernel<CI, NC>, grid, dim3(512), lds, s, (const bf16_t*)x, xp, (const bf16_t*)wt0,
+                 (const bf16_t*)dz, (const bf16_t*)yd, w, (bf16_t*)dx, sl, gparts, H, W, C, pad_t, pad_l, Ho, Wo, t, ep,
+                 bd);
+    });
+  });
+  ROD_CHECK_ARG(hit, "rod_dw3x3_bwd_fused_rc: no kernel for Cin=%d nct=%d", Cin, nct);
   const int rc = check_launch("rod_dw3x3_bwd_fused_rc");
   if (rc) return rc;
   slab_sum(sl, dw, (int)((long)N * t.strips * t.coltiles), 9L * C, s);

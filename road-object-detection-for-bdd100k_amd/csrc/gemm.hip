@@ -1131,19 +1131,13 @@ static bool pw_stream_launch(const bf16_t* x, const bf16_t* wt, bf16_t* y, long 
     const long per = cdivl(ntiles, maxw);
     const dim3 grid((unsigned)cdivl(cdivl(ntiles, per), PWS_WAVES), ng);
     const BnGred g{};
-#define PWN(NT_)                                                                                               \
-  if (nt == NT_) {                                                                                             \
-    if (pro)                                                                                                   \
-      hipLaunchKernelGGL((pw_stream_kernel<NT_, 1, 3, true>), grid, dim3(256), 0, s, x, wt, y, M, K, Cout, ldx, \
-                         ldy, stats, g, pv);                                                                   \
-    else                                                                                                       \
-      hipLaunchKernelGGL((pw_stream_kernel<NT_, 1, 3>), grid, dim3(256), 0, s, x, wt, y, M, K, Cout, ldx, ldy,  \
-                         stats, g);                                                                            \
-    return true;                                                                                               \
-  }
-    PWN(2) PWN(3) PWN(4) PWN(6) PWN(8) PWN(9) PWN(12)
-#undef PWN
-    return false;
+    // nt: one of pw_stream_groups' widths; MODE 3 (statistics only) is built for one k step
+    return sel_int<2, 3, 4, 6, 8, 9, 12>(nt, [&](auto NT) {
+      sel_bool(pro != nullptr, [&](auto PRO) {
+        hipLaunchKernelGGL((pw_stream_kernel<NT, 1, 3, PRO>), grid, dim3(256), 0, s, x, wt, y, M, K, Cout, ldx, ldy,
+                           stats, g, pv);
+      });
+    });
   }
   int nt = 0;
   const int ng = pw_stream_groups(M, K, Cout, nt, gr != nullptr);
@@ -1157,40 +1151,25 @@ static bool pw_stream_launch(const bf16_t* x, const bf16_t* wt, bf16_t* y, long 
   const long per = cdivl(ntiles, maxw);
   const dim3 grid((unsigned)cdivl(cdivl(ntiles, per), PWS_WAVES), ng);
   const BnGred g = gr ? *gr : BnGred{};
-#define PWS(NT_, KT_)                                                                                           \
-  do {                                                                                                          \
-    if constexpr (KT_ == 1) {                                                                                   \
-      if (pro) {                                                                                                \
-        if (stats)                                                                                              \
-          hipLaunchKernelGGL((pw_stream_kernel<NT_, 1, 1, true>), grid, dim3(256), 0, s, x, wt, y, M, K, Cout,  \
-                             ldx, ldy, stats, g, *pro);                                                         \
-        else                                                                                                    \
-          hipLaunchKernelGGL((pw_stream_kernel<NT_, 1, 0, true>), grid, dim3(256), 0, s, x, wt, y, M, K, Cout,  \
-                             ldx, ldy, nullptr, g, *pro);                                                       \
-        return true;                                                                                            \
-      }                                                                                                         \
-    }                                                                                                           \
-    if (gr)                                                                                                     \
-      hipLaunchKernelGGL((pw_stream_kernel<NT_, KT_, 2>), grid, dim3(256), 0, s, x, wt, y, M, K, Cout, ldx, ldy, \
-                         nullptr, g);                                                                           \
-    else if (stats)                                                                                             \
-      hipLaunchKernelGGL((pw_stream_kernel<NT_, KT_, 1>), grid, dim3(256), 0, s, x, wt, y, M, K, Cout, ldx, ldy, \
-                         stats, g);                                                                             \
-    else                                                                                                        \
-      hipLaunchKernelGGL((pw_stream_kernel<NT_, KT_, 0>), grid, dim3(256), 0, s, x, wt, y, M, K, Cout, ldx, ldy, \
-                         nullptr, g);                                                                           \
-    return true;                                                                                                \
-  } while (0)
-#define PWK(NT_)                  \
-  if (nt == NT_) {                \
-    if (kt == 1) PWS(NT_, 1);     \
-    else if (kt == 2) PWS(NT_, 2); \
-    else PWS(NT_, 3);             \
-  }
-  PWK(2) PWK(3) PWK(4) PWK(6) PWK(8) PWK(9) PWK(12)
-#undef PWK
-#undef PWS
-  return false;
+  // MODE: 2 the gred sums, 1 the statistics parts, 0 neither; the prologue forms are built for
+  // one k step and MODE 0 / 1 only (checked above)
+  const int mode = gr ? 2 : stats ? 1 : 0;
+  float* const st = mode == 1 ? stats : nullptr;
+  return sel_int<2, 3, 4, 6, 8, 9, 12>(nt, [&](auto NT) {
+    return sel_int<1, 2, 3>(kt, [&](auto KT) {
+      if constexpr (KT == 1) {
+        if (pro)
+          return sel_int<0, 1>(mode, [&](auto MODE) {
+            hipLaunchKernelGGL((pw_stream_kernel<NT, 1, MODE, true>), grid, dim3(256), 0, s, x, wt, y, M, K, Cout,
+                               ldx, ldy, st, g, *pro);
+          });
+      }
+      return sel_int<0, 1, 2>(mode, [&](auto MODE) {
+        hipLaunchKernelGGL((pw_stream_kernel<NT, KT, MODE>), grid, dim3(256), 0, s, x, wt, y, M, K, Cout, ldx, ldy, st,
+                           g);
+      });
+    });
+  });
 }
 
 // The projects (the streaming form past K = 96): a 1x1 conv whose input
@@ -1217,29 +1196,15 @@ static bool pw_proj_launch(const bf16_t* x, const bf16_t* wt, bf16_t* y, long M,
   const long per = cdivl(ntiles, maxw);
   const dim3 grid((unsigned)cdivl(cdivl(ntiles, per), PWS_WAVES), 1);
   const BnGred g{};
-#define PJ(NT_, KT_)                                                                                             \
-  do {                                                                                                           \
-    if (stats)                                                                                                   \
-      hipLaunchKernelGGL((pw_stream_kernel<NT_, KT_, 1, true>), grid, dim3(256), 0, s, x, wt, y, M, K, Cout, ldx, \
-                         ldy, stats, g, pro);                                                                    \
-    else                                                                                                         \
-      hipLaunchKernelGGL((pw_stream_kernel<NT_, KT_, 0, true>), grid, dim3(256), 0, s, x, wt, y, M, K, Cout, ldx, \
-                         ldy, nullptr, g, pro);                                                                  \
-    return true;                                                                                                 \
-  } while (0)
-#define PJK(NT_)                     \
-  switch (kt) {                      \
-    case 1: PJ(NT_, 1);              \
-    case 2: PJ(NT_, 2);              \
-    case 3: PJ(NT_, 3);              \
-    case 4: PJ(NT_, 4);              \
-    case 5: PJ(NT_, 5);              \
-    default: PJ(NT_, 6);             \
-  }
-  if (nt == 1) PJK(1) else PJK(2)
-#undef PJK
-#undef PJ
-  return false;
+  // nt is 1 or 2 (Cout <= 32), kt 2 .. 6 (K <= 192; kt 1 returned above, its form is still built)
+  return sel_int<1, 2>(nt, [&](auto NT) {
+    return sel_int<1, 2, 3, 4, 5, 6>(kt, [&](auto KT) {
+      sel_bool(stats != nullptr, [&](auto ST) {
+        hipLaunchKernelGGL((pw_stream_kernel<NT, KT, ST ? 1 : 0, true>), grid, dim3(256), 0, s, x, wt, y, M, K, Cout,
+                           ldx, ldy, stats, g, pro);
+      });
+    });
+  });
 }
 
 // split-K combine: y[m, co] = round(sum_s part[s][m][co] + bias[co]), fixed split order
@@ -2090,8 +2055,11 @@ static void conv_fwd_dispatch(bool va, bool vb, bool vy, const void* x, const vo
                               long M, int H, int W, int Cin, int Cout, int ldx, int ldy, float* stats,
                               const BnPro& pro, const BnGred* gr, hipStream_t s, const BnEpi* ep = nullptr,
                               const BnBwd* bw = nullptr) {
-#define CF(BN_, VA_, VB_, VY_) \
-  conv_fwd_launch<T, KS, BN_, VA_, VB_, VY_, PRO>(x, wt, bias, y, M, H, W, Cin, Cout, ldx, ldy, stats, pro, gr, s, ep, bw)
+  // VB == VY in every form built: 16-byte B rows go with the LDS-staged (vector) epilogue
+  auto cf = [&](auto BN_, auto VA_, auto VY_) {
+    conv_fwd_launch<T, KS, BN_, VA_, VY_, VY_, PRO>(x, wt, bias, y, M, H, W, Cin, Cout, ldx, ldy, stats, pro, gr, s, ep,
+                                                    bw);
+  };
   if (va && vb && vy) {
     if constexpr (sizeof(T) == 2) {
       const int K = KS * KS * Cin;
@@ -2102,30 +2070,18 @@ static void conv_fwd_dispatch(bool va, bool vb, bool vy, const void* x, const vo
         return;
       }
     }
-    if (Cout <= 32) CF(32, true, true, true);
-    else if (Cout <= 64) CF(64, true, true, true);
-    else if (Cout <= 96) CF(96, true, true, true);
-    else if (Cout <= 128) CF(128, true, true, true);
-    else if (Cout <= 160) CF(160, true, true, true);
-    else if (Cout <= 192) CF(192, true, true, true);
-    else if (Cout <= 256) CF(256, true, true, true);
-    else CF(128, true, true, true);
+    const int bn = Cout <= 192 ? cdiv(Cout, 32) * 32 : Cout <= 256 ? 256 : 128;
+    sel_int<32, 64, 96, 128, 160, 192, 256>(bn, [&](auto BN_) { cf(BN_, std::true_type{}, std::true_type{}); });
     return;
   }
   // direct-store epilogue (Cout or ldy not a multiple of 8: the heads' last convs, 4 / 11 x
   // anchors channels): the N tile is the smallest of 32 / 64 / 96 / 128 covering Cout (a 128-wide
   // tile for 36 or 66 outputs wasted half the MFMAs and B loads); B rows load in G-element
   // pieces (VB false), which also covers the aligned case at two 8-byte loads per chunk
-  if (Cout <= 32) {
-    if (va) CF(32, true, false, false); else CF(32, false, false, false);
-  } else if (Cout <= 64) {
-    if (va) CF(64, true, false, false); else CF(64, false, false, false);
-  } else if (Cout <= 96) {
-    if (va) CF(96, true, false, false); else CF(96, false, false, false);
-  } else {
-    if (va) CF(128, true, false, false); else CF(128, false, false, false);
-  }
-#undef CF
+  const int bn = Cout <= 96 ? cdiv(Cout, 32) * 32 : 128;
+  sel_int<32, 64, 96, 128>(bn, [&](auto BN_) {
+    sel_bool(va, [&](auto VA_) { cf(BN_, VA_, std::false_type{}); });
+  });
 }
 
 template <typename T, int KS, bool PRO, bool VA, bool VB>

@@ -1088,37 +1088,24 @@ static int pw_bwd_run(const void* dz, const void* y, const void* wt0, const floa
                 mean, rstd, gamma, beta, coef, xmean, xrstd, xgamma, xbeta, act, xact, M, 0, Cin, Cout, 0, 0, 0, 0,
                 nullptr, (const bf16_t*)wt0};
     const long ntiles = cdivl(M, 32);
-#define PBS0(CI, CO, PR, DXF, XLN, RCF)                                                                         \
-  do {                                                                                                          \
-    const size_t lds = PbsGeo<CI, CO>::lds(RCF);                                                                \
-    (void)hipFuncSetAttribute((const void*)pw_bwd_stream_kernel<CI, CO, PR, DXF, false, XLN, RCF>,              \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                            \
-    hipLaunchKernelGGL((pw_bwd_stream_kernel<CI, CO, PR, DXF, false, XLN, RCF>), dim3(nblk), dim3(256), lds, s, \
-                       a, ntiles, nullptr);                                                                     \
-  } while (0)
-#define PBS1(CI, CO, PR, DXF, XLN)                  \
-  do {                                              \
-    if (wt0) PBS0(CI, CO, PR, DXF, XLN, true);      \
-    else PBS0(CI, CO, PR, DXF, XLN, false);         \
-  } while (0)
-#define PBS(CI, CO, PR, DXF)                                      \
-  do {                                                            \
-    if (PR && xact == ROD_ACT_NONE) PBS1(CI, CO, PR, DXF, true);  \
-    else PBS1(CI, CO, PR, DXF, false);                            \
-  } while (0)
-#define PBS2(CI, CO)                                        \
-  if (Cin == CI) {                                          \
-    if (xmean) {                                            \
-      if (dx) PBS(CI, CO, true, true); else PBS(CI, CO, true, false);   \
-    } else {                                                \
-      if (dx) PBS(CI, CO, false, true); else PBS(CI, CO, false, false); \
-    }                                                       \
-  }
-    PBS2(16, 96) else PBS2(24, 144)
-#undef PBS2
-#undef PBS
-#undef PBS1
-#undef PBS0
+    // PR: input prologue, DXF: dx wanted, XL: the prologue without an activation (built for
+    // either PR, selected only with it), RCF: y recomputed from wt0
+    auto go = [&](auto CI, auto CO) {
+      sel_bool(xmean != nullptr, [&](auto PR) {
+        sel_bool(dx != nullptr, [&](auto DXF) {
+          sel_bool(PR && xact == ROD_ACT_NONE, [&](auto XL) {
+            sel_bool(wt0 != nullptr, [&](auto RCF) {
+              const size_t lds = PbsGeo<CI, CO>::lds(RCF);
+              launch_lds(pw_bwd_stream_kernel<CI, CO, PR, DXF, false, XL, RCF>, dim3(nblk), dim3(256), lds, s, a,
+                         ntiles, nullptr);
+            });
+          });
+        });
+      });
+    };
+    if (Cin == 16 && Cout == 96) go(int_c<16>{}, int_c<96>{});
+    else if (Cin == 24 && Cout == 144) go(int_c<24>{}, int_c<144>{});
+    else ROD_CHECK_ARG(false, "rod_pw_bwd: no streaming kernel for Cin=%d Cout=%d", Cin, Cout);
     slab_sum(partw, dw, nblk, (long)Cout * Cin, s);
     return check_launch("rod_pw_bwd");
   }
@@ -1126,23 +1113,13 @@ static int pw_bwd_run(const void* dz, const void* y, const void* wt0, const floa
   PwBwdArgs a{(const bf16_t*)dz, (const bf16_t*)y, (const bf16_t*)x, (const bf16_t*)wt1, (bf16_t*)dx, partw, partb,
               mean, rstd, gamma, beta, coef, xmean, xrstd, xgamma, xbeta, act, xact, M, p.chunk,
               Cin, Cout, p.kd, p.nci, p.nco, p.nxt};
-#define PBL(NX_, WT_)                                                                                  \
-  do {                                                                                                 \
-    (void)hipFuncSetAttribute((const void*)pw_bwd_kernel<NX_, WT_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                        (int)p.lds);                                                                   \
-    hipLaunchKernelGGL((pw_bwd_kernel<NX_, WT_>), dim3(p.nblk), dim3(256), p.lds, s, a);               \
-  } while (0)
-#define PBW(NX_)                   \
-  if (p.wt == 4) PBL(NX_, 4);      \
-  else if (p.wt == 6) PBL(NX_, 6); \
-  else if (p.wt == 8) PBL(NX_, 8); \
-  else PBL(NX_, 16)
-  if (p.nx == 2) PBW(2);
-  else if (p.nx == 4) PBW(4);
-  else if (p.nx == 8) PBW(8);
-  else PBW(12);
-#undef PBW
-#undef PBL
+  // p.nx is 2 / 4 / 8 / 12 A tiles and p.wt 4 / 6 / 8 / 16 weight tiles per wave (pw_bwd_plan)
+  const bool hit = sel_int<2, 4, 8, 12>(p.nx, [&](auto NX) {
+    return sel_int<4, 6, 8, 16>(p.wt, [&](auto WT) {
+      launch_lds(pw_bwd_kernel<NX, WT>, dim3(p.nblk), dim3(256), p.lds, s, a);
+    });
+  });
+  ROD_CHECK_ARG(hit, "rod_pw_bwd: no kernel for nx=%d wt=%d", p.nx, p.wt);
   slab_sum(partw, dw, p.nblk, (long)Cout * Cin, s);
   if (db) slab_sum(partb, db, p.nblk, (long)Cout, s);
   return check_launch("rod_pw_bwd");
@@ -1211,28 +1188,13 @@ static int pw_bwd_gred_run(const void* dz, const void* y, const float* mean, con
                 nullptr, mean, rstd, gamma, beta, coef, xmean, xrstd, xgamma, xbeta, act, xact, M, 0, Cin, Cout, 0, 0,
                 0, 0, nullptr, (const bf16_t*)wt0};
     const long nt = cdivl(M, 32);
-#define PBX0(CI, CO, XLN, RCF)                                                                                 \
-  do {                                                                                                         \
-    const size_t lds = PbsGeo<CI, CO>::lds(RCF);                                                               \
-    (void)hipFuncSetAttribute((const void*)pw_bwd_stream_kernel<CI, CO, true, true, true, XLN, RCF>,           \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
-    hipLaunchKernelGGL((pw_bwd_stream_kernel<CI, CO, true, true, true, XLN, RCF>), dim3(nb), dim3(256), lds, s, a, \
-                       nt, xparts);                                                                            \
-  } while (0)
-#define PBX1(CI, CO, XLN)                      \
-  do {                                         \
-    if (wt0) PBX0(CI, CO, XLN, true);          \
-    else PBX0(CI, CO, XLN, false);             \
-  } while (0)
-#define PBX(CI, CO)                                          \
-  if (Cin == CI) {                                           \
-    if (xact == ROD_ACT_NONE) PBX1(CI, CO, true);            \
-    else PBX1(CI, CO, false);                                \
-  }
-    PBX(16, 96)
-#undef PBX
-#undef PBX1
-#undef PBX0
+    // sexp: 16 -> 96 only (pw_bwd_xg_ok)
+    sel_bool(xact == ROD_ACT_NONE, [&](auto XL) {
+      sel_bool(wt0 != nullptr, [&](auto RCF) {
+        const size_t lds = PbsGeo<16, 96>::lds(RCF);
+        launch_lds(pw_bwd_stream_kernel<16, 96, true, true, true, XL, RCF>, dim3(nb), dim3(256), lds, s, a, nt, xparts);
+      });
+    });
     slab_sum(partw, dw, nb, (long)Cout * Cin, s);
     return check_launch("rod_pw_bwd_gred");
   }
@@ -1246,31 +1208,18 @@ static int pw_bwd_gred_run(const void* dz, const void* y, const float* mean, con
   // 569 vs 433 us), so there the per-element form runs (ROD_PWB_GRED_FAST48=1: packed, A/B)
   static const bool fast48 = getenv("ROD_PWB_GRED_FAST48") && atoi(getenv("ROD_PWB_GRED_FAST48")) == 1;
   const bool fast = act == ROD_ACT_NONE && xact == ROD_ACT_RELU6 && (nw == 32 || fast48);
-#define PBGD(CO, NW_, F, D)                                                                                     \
-  do {                                                                                                          \
-    const size_t lds = PbgGeo<CO, NW_>::lds();                                                                  \
-    (void)hipFuncSetAttribute((const void*)pw_bwd_gred_kernel<CO, NW_, F, D>,                                   \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                            \
-    hipLaunchKernelGGL((pw_bwd_gred_kernel<CO, NW_, F, D>), grid, dim3(256), lds, s, a, ntiles, xparts);        \
-  } while (0)
-#define PBG(CO, NW_, F)                  \
-  do {                                   \
-    if (dyp) PBGD(CO, NW_, F, true);     \
-    else PBGD(CO, NW_, F, false);        \
-  } while (0)
-#define PBG1(CO, NW_)                        \
-  if (fast) PBG(CO, NW_, true);              \
-  else PBG(CO, NW_, false);
-#define PBG2(CO)                                                                    \
-  if (Cout == CO) {                                                                 \
-    if (nw == 48 && CO != 64) { PBG1(CO, 48) }                                      \
-    else { PBG1(CO, 32) }                                                           \
-  }
-  PBG2(16) else PBG2(24) else PBG2(32) else PBG2(64)
-#undef PBG2
-#undef PBG1
-#undef PBG
-#undef PBGD
+  // Cout 16 / 24 / 32 / 64 in groups of nw = 32 or 48 columns (pw_bwd_gred_nw; it gives Cout 64
+  // 32 only, so the <64, 48> forms are built but never selected)
+  const bool hit = sel_int<16, 24, 32, 64>(Cout, [&](auto CO) {
+    return sel_int<32, 48>(nw, [&](auto NW) {
+      sel_bool(fast, [&](auto F) {
+        sel_bool(dyp != nullptr, [&](auto D) {
+          launch_lds(pw_bwd_gred_kernel<CO, NW, F, D>, grid, dim3(256), PbgGeo<CO, NW>::lds(), s, a, ntiles, xparts);
+        });
+      });
+    });
+  });
+  ROD_CHECK_ARG(hit, "rod_pw_bwd_gred: no kernel for Cout=%d nw=%d", Cout, nw);
   slab_sum(partw, dw, nblk, (long)Cout * Cin, s);
   return check_launch("rod_pw_bwd_gred");
 }

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 
 #include "../../include/rod.h"
 
@@ -289,6 +290,41 @@ __device__ __forceinline__ void gred_acc(float dz, float y, float sc, float sh, 
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 inline long cdivl(long a, long b) { return (a + b - 1) / b; }
+
+// ---- host-side dispatch: a runtime value -> a compile-time constant -------------------
+// sel_int<A, B, ...>(v, f) calls f(int_c<X>{}) for the alternative X equal to v, sel_bool(b, f)
+// f(std::true_type{} / std::false_type{}), sel_dtype(dt, f) f(float{} / bf16_t{}); f is a
+// generic lambda and its argument converts to the constant wherever one is needed
+// (kernel<S, V, ...>).  Each returns false when v is none of the alternatives — or when f
+// itself returns false, so a nest of selections reports a miss at any depth (an f returning
+// void counts as done); the entry turns that into ROD_EINVAL.  Every alternative listed is
+// instantiated: an axis that must not form the full product is cut with `if constexpr` in f.
+template <int X> using int_c = std::integral_constant<int, X>;
+template <typename F, typename Tag>
+inline bool sel_call(F& f, Tag tag) {
+  if constexpr (std::is_void_v<decltype(f(tag))>) return f(tag), true;
+  else return f(tag);
+}
+template <int... Xs, typename F>
+inline bool sel_int(int v, F&& f) {
+  bool ok = false;
+  (void)((v == Xs && ((ok = sel_call(f, int_c<Xs>{})), true)) || ...);
+  return ok;
+}
+template <typename F>
+inline bool sel_bool(bool b, F&& f) {
+  return b ? sel_call(f, std::true_type{}) : sel_call(f, std::false_type{});
+}
+template <typename F>
+inline bool sel_dtype(int dtype, F&& f) {
+  return dtype == ROD_F32 ? sel_call(f, float{}) : dtype == ROD_BF16 && sel_call(f, bf16_t{});
+}
+// launch of one instantiation with its dynamic-LDS limit raised first (both on every call)
+template <typename... P, typename... A>
+inline void launch_lds(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, A... args) {
+  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kern, grid, block, lds, s, args...);
+}
 
 }  // namespace rod
 
