@@ -117,6 +117,18 @@ def det_clf_loss(det_out, det_gt, det_pos, clf_logits, det_lbl, iou, lvl_off, bs
             'g_logits': g.reshape(B, A, K).astype(f32), 'iouf': iouf}
 
 
+def smooth_l1_levels(pred, target, mask, lvl_off, bs):
+    """Per-level smooth-L1 sums (refine_loss / the det_loss term, net_tools.py:486-515):
+    float32 per element, float64 sum per level, / bs; returns ([L] per-level, their total)."""
+    m = np.asarray(mask).astype(f32)[..., None]
+    d = (np.asarray(target, f32) - np.asarray(pred, f32)) * m
+    ad = np.abs(d)
+    sl1 = f32(0.5) * ((ad - f32(1)) * np.minimum(ad, f32(1)) + ad)
+    lv = np.array([np.sum(sl1[:, lvl_off[l]:lvl_off[l + 1]], dtype=np.float64) / bs
+                   for l in range(len(lvl_off) - 1)])
+    return lv, float(lv.sum())
+
+
 def tf_nms_iou(bi, bj):
     """IOU of tensorflow/core/kernels/non_max_suppression_op.cc (TF 1.x)."""
     ymin_i, xmin_i = min(bi[0], bi[2]), min(bi[1], bi[3])
