@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ROD_ABI_VERSION 25
+#define ROD_ABI_VERSION 26
 #define ROD_EINVAL (-1)
 
 enum { ROD_F32 = 0, ROD_BF16 = 1, ROD_I32 = 2 /* collectives only (ABI 19) */ };
@@ -642,6 +642,40 @@ int rod_hnm_radix_scan(int shift, int* state, unsigned* hist, void* stream);
 int rod_hnm_loss(const void* logits, const int* det_lbl, const int* det_pos, const float* iou,
                  const int* lvl_off, int L, float bs, const int* state, float* out, void* grad,
                  void* workspace, int B, int A, int K, int dtype, void* stream);
+/* Focal loss (Lin et al., ICCV 2017; ABI 26; opt-in, the reference has none) for the ODM
+ * classifier, in place of BOTH the hard-negative mining and the IoU factor above: one pass over
+ * the logits, no selection, no dependence on iou.  Rows r = 0..B*A-1, pos = det_pos != 0, target
+ * t = det_lbl if pos else 0; per row in fp32 with the correctly-rounded exp / log:
+ *   m = max_k x_k, e_k = exp(x_k - m), s = sum_k e_k, p_k = e_k / s,
+ *   q = (s - e_t) / s   (1 - p_t without the cancellation; never negative),
+ *   lp = (x_t - m) - log(s),  a = alpha if pos else 1 - alpha,
+ *   w = q^gamma  (1 when gamma == 0, also at q == 0; 0 when q == 0 and gamma > 0),
+ *   FL = -a w lp,
+ *   dFL/dx_k = a (delta_kt - p_k) (gamma q^(gamma-1) p_t lp - w), delta_tt - p_t taken as q and
+ *              the first term of the last bracket as 0 when q == 0 (its limit for gamma > 0).
+ * n_pos = sum pos over the GLOBAL batch, norm = max(n_pos, 1); pos_loss = sum_pos FL / norm,
+ * neg_loss = sum_neg FL / norm, clf_loss = pos_loss + neg_loss; grad = dFL/dx / norm rounded once
+ * to the logits' dtype.  Row sums are fp64 per block and per slab in a fixed order (no float
+ * atomics): run-to-run bit-identical.
+ * logits [B*A, K] (dtype), 2 <= K <= 16; det_lbl / det_pos int [B*A]; 0 <= alpha <= 1; gamma
+ * finite, >= 0 (checked on the host before any launch; the message names the argument).
+ * out fp32 [8] (device): pos_loss, neg_loss, clf_loss, 0, n_pos, 0, n_neg, norm.
+ * grad (nullable, dtype [B*A, K]); logits and grad need only their element's alignment.
+ * rod_softmax_focal = rod_focal_count + rod_focal_loss back to back with the counts kept in the
+ * workspace: three kernels (count, loss, finalize) behind one 8-byte memset node that clears the
+ * counts; no host synchronisation, no allocation: capturable in a graph.
+ * Data parallel: rod_focal_count -> counts2[2] = (n_pos, n_neg) of this rank's rows
+ * [caller: all-reduce SUM], then rod_focal_loss with the global counts -> out / grad of its
+ * rows (out[0..2] are this rank's share of the global sums, out[4], [6], [7] global).
+ * counts2 is a caller-owned device array; workspace: rod_softmax_focal_workspace() bytes. */
+size_t rod_softmax_focal_workspace(int B, int A);
+int rod_softmax_focal(const void* logits, const int* det_lbl, const int* det_pos, float alpha,
+                      float gamma, float* out, void* grad, void* workspace, int B, int A, int K,
+                      int dtype, void* stream);
+int rod_focal_count(const int* det_pos, void* workspace, int* counts2, int B, int A, void* stream);
+int rod_focal_loss(const void* logits, const int* det_lbl, const int* det_pos, const int* counts2,
+                   float alpha, float gamma, float* out, void* grad, void* workspace, int B, int A,
+                   int K, int dtype, void* stream);
 
 /* ------------------------------------------------ post-processing (A15)
  * detected_bboxes (net_tools.py:739-758) for every image and class 1..K-1: select

@@ -9,6 +9,9 @@
 //   pos_loss = sum CE(label) * pos * iouf / bs;  neg_loss = sum CE(0) * negmask / bs (605-613)
 //   clf_loss = neg_loss / 2 + pos_loss                                             (615)
 // plus d clf_loss / d logits.  Row layout: [B, A] anchors (levels concatenated per image).
+//
+// Opt-in alternative (rod_softmax_focal, not in the reference): focal loss over every row in one
+// pass, without the selection and without the IoU factor; semantics in include/rod.h.
 #include <math.h>
 
 #include "rod_common.h"
@@ -489,6 +492,244 @@ static HnmWs carve(void* ws, long R, int B, int L, int nb) {
   return w;
 }
 
+// ---- focal loss (include/rod.h, ABI 26): count -> loss -> finalize ----------------------------
+// workspace: [0, 256) counts2 of the single-process form, then the loss slab [nb][2] fp64
+constexpr int FOCAL_ROWS = 256;  // rows per block pass = threads per block
+
+// counts2 += (positives, negatives) of pos[0, R): 16-byte loads between a scalar head and tail,
+// one pair of integer atomics per block (integer sums: the order does not matter)
+__global__ void __launch_bounds__(256) focal_count_kernel(const int* __restrict__ pos, long R,
+                                                          int* __restrict__ counts2) {
+  __shared__ int red[2][4];
+  typedef int i32x4 __attribute__((ext_vector_type(4)));
+  const long h = (long)(((16 - ((uintptr_t)pos & 15)) & 15) / 4);  // pos is 4-byte aligned
+  const long head = h < R ? h : R;
+  const long nv = (R - head) / 4;
+  const long tail0 = head + nv * 4;
+  const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long gs = (long)gridDim.x * blockDim.x;
+  int np = 0, nn = 0;
+  if (g < head) {
+    np += pos[g] != 0;
+    nn += pos[g] == 0;
+  }
+  for (long v = g; v < nv; v += gs) {
+    const i32x4 p = *(const i32x4*)(pos + head + v * 4);
+    const int c = (p[0] != 0) + (p[1] != 0) + (p[2] != 0) + (p[3] != 0);
+    np += c;
+    nn += 4 - c;
+  }
+  if (tail0 + g < R) {  // at most 3 elements
+    np += pos[tail0 + g] != 0;
+    nn += pos[tail0 + g] == 0;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    np += __shfl_xor(np, o, 64);
+    nn += __shfl_xor(nn, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = np;
+    red[1][threadIdx.x >> 6] = nn;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int bp = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+    const int bn = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    if (bp) atomicAdd(&counts2[0], bp);
+    if (bn) atomicAdd(&counts2[1], bn);
+  }
+}
+
+// A block pass handles FOCAL_ROWS consecutive rows = one contiguous span of n <= 256 K elements.
+// The span is copied between global memory and LDS with 16-byte vectors; `buf` is the LDS array
+// already shifted by the span's misalignment (in elements) so that a 16-byte aligned global
+// address is a 16-byte aligned LDS address.  The elements before the first and after the last
+// aligned vector of the span go one at a time.
+template <typename T>
+__device__ __forceinline__ int span_mis(const T* g) {
+  return (int)(((uintptr_t)g / sizeof(T)) % Vec16<T>::N);
+}
+template <typename T, bool IN>
+__device__ __forceinline__ void span_copy(T* g, T* buf, int mis, int n) {
+  constexpr int VN = Vec16<T>::N;
+  const int head = min(n, (VN - mis) % VN);
+  const int nv = (n - head) / VN;
+  const int tail0 = head + nv * VN;
+  const int tid = threadIdx.x;
+  if (tid < head) {
+    if constexpr (IN) buf[tid] = g[tid];
+    else g[tid] = buf[tid];
+  }
+  for (int v = tid; v < nv; v += FOCAL_ROWS) {
+    Vec16<T> x;
+    if constexpr (IN) {
+      x.load(g + head + v * VN);
+      x.store(buf + head + v * VN);
+    } else {
+      x.load(buf + head + v * VN);
+      x.store_out(g + head + v * VN);
+    }
+  }
+  if (tail0 + tid < n) {
+    if constexpr (IN) buf[tail0 + tid] = g[tail0 + tid];
+    else g[tail0 + tid] = buf[tail0 + tid];
+  }
+}
+
+template <typename T, bool GRAD>
+__global__ void __launch_bounds__(256) focal_loss_kernel(const T* __restrict__ logits, const int* __restrict__ lbl,
+                                                         const int* __restrict__ pos,
+                                                         const int* __restrict__ counts2, float alpha, float gamma,
+                                                         long R, int K, T* __restrict__ grad,
+                                                         double* __restrict__ slab) {
+  constexpr int VN = Vec16<T>::N;
+  __shared__ __attribute__((aligned(16))) T sm[FOCAL_ROWS * HNM_K + VN];
+  __shared__ double red[2][4];
+  const int tid = threadIdx.x;
+  const float norm = (float)max(counts2[0], 1);
+  const long nrb = (R + FOCAL_ROWS - 1) / FOCAL_ROWS;
+  double sp = 0.0, sn = 0.0;
+  for (long rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
+    const long r0 = rb * FOCAL_ROWS;
+    const int rows = R - r0 < FOCAL_ROWS ? (int)(R - r0) : FOCAL_ROWS;
+    const long e0 = r0 * K;
+    const int n = rows * K;
+    const int mis = span_mis(logits + e0);
+    span_copy<T, true>(const_cast<T*>(logits) + e0, sm + mis, mis, n);
+    __syncthreads();
+    float e[HNM_K];
+    float coef = 0.f, q = 0.f;
+    int t = 0;
+    if (tid < rows) {
+      const T* x = sm + mis + tid * K;
+      const bool p = pos[r0 + tid] != 0;
+      t = p ? lbl[r0 + tid] : 0;
+      float m = to_f32(x[0]);
+#pragma unroll
+      for (int k = 0; k < HNM_K; ++k)
+        if (k < K) {
+          e[k] = to_f32(x[k]);
+          m = fmaxf(m, e[k]);
+        }
+      float s = 0.f, et = 0.f, dt = 0.f;
+#pragma unroll
+      for (int k = 0; k < HNM_K; ++k)
+        if (k < K) {
+          const float d = e[k] - m;
+          e[k] = exp_cr(d);
+          s += e[k];
+          if (k == t) {
+            et = e[k];
+            dt = d;
+          }
+        }
+      q = (s - et) / s;
+      const float pt = et / s;
+      const float lp = dt - log_cr(s);
+      const float a = p ? alpha : 1.f - alpha;
+      const float w = gamma == 0.f ? 1.f : (q == 0.f ? 0.f : powf(q, gamma));
+      const float fl = -(a * w * lp);
+      if (p) sp += (double)fl;
+      else sn += (double)fl;
+      if constexpr (GRAD) {
+        const float t1 = (gamma > 0.f && q > 0.f) ? gamma * (w / q) * pt * lp : 0.f;
+        coef = a * (t1 - w) / norm;
+#pragma unroll
+        for (int k = 0; k < HNM_K; ++k)
+          if (k < K) e[k] = e[k] / s;  // p_k
+      }
+    }
+    if constexpr (GRAD) {
+      const int misg = span_mis(grad + e0);
+      __syncthreads();  // every row has been read: the buffer now takes the gradient
+      if (tid < rows) {
+        T* gx = sm + misg + tid * K;
+#pragma unroll
+        for (int k = 0; k < HNM_K; ++k)
+          if (k < K) gx[k] = from_f32<T>((k == t ? q : -e[k]) * coef);
+      }
+      __syncthreads();
+      span_copy<T, false>(grad + e0, sm + misg, misg, n);
+    }
+    __syncthreads();  // before the next pass overwrites the buffer
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    sp += __shfl_xor(sp, o, 64);
+    sn += __shfl_xor(sn, o, 64);
+  }
+  if ((tid & 63) == 0) {
+    red[0][tid >> 6] = sp;
+    red[1][tid >> 6] = sn;
+  }
+  __syncthreads();
+  if (tid == 0)
+    for (int j = 0; j < 2; ++j) slab[blockIdx.x * 2 + j] = red[j][0] + red[j][1] + red[j][2] + red[j][3];
+}
+
+__global__ void focal_finalize_kernel(const double* __restrict__ slab, int nb, const int* __restrict__ counts2,
+                                      float* __restrict__ out) {
+  __shared__ double s[2][256];
+  double a = 0, b = 0;
+  for (int i = threadIdx.x; i < nb; i += 256) {
+    a += slab[i * 2];
+    b += slab[i * 2 + 1];
+  }
+  s[0][threadIdx.x] = a;
+  s[1][threadIdx.x] = b;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w)
+      for (int j = 0; j < 2; ++j) s[j][threadIdx.x] += s[j][threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const int norm = max(counts2[0], 1);
+    const float pos_loss = (float)(s[0][0] / (double)norm);
+    const float neg_loss = (float)(s[1][0] / (double)norm);
+    out[0] = pos_loss;
+    out[1] = neg_loss;
+    out[2] = pos_loss + neg_loss;
+    out[3] = 0.f;
+    out[4] = (float)counts2[0];
+    out[5] = 0.f;
+    out[6] = (float)counts2[1];
+    out[7] = (float)norm;
+  }
+}
+
+static int focal_check(const char* who, int B, int A, int K, float alpha, float gamma) {
+  ROD_CHECK_ARG(B > 0 && A > 0, "%s: B and A must be > 0 (got B %d, A %d)", who, B, A);
+  ROD_CHECK_ARG(K >= 2 && K <= HNM_K, "%s: K must be in 2..16 (got %d)", who, K);
+  ROD_CHECK_ARG(isfinite(gamma) && gamma >= 0.f, "%s: gamma must be finite and >= 0 (got %g)", who, (double)gamma);
+  ROD_CHECK_ARG(alpha >= 0.f && alpha <= 1.f, "%s: alpha must be in [0, 1] (got %g)", who, (double)alpha);
+  return 0;
+}
+
+static int focal_count(const int* det_pos, int* counts2, long R, hipStream_t s) {
+  hipError_t e = hipMemsetAsync(counts2, 0, 2 * sizeof(int), s);
+  if (e != hipSuccess) {
+    set_error("rod_focal_count: hipMemsetAsync: %s", hipGetErrorString(e));
+    return (int)e;
+  }
+  hipLaunchKernelGGL(focal_count_kernel, dim3(hnm_blocks(cdivl(R, 4))), dim3(256), 0, s, det_pos, R, counts2);
+  return 0;
+}
+
+static void focal_loss(const void* logits, const int* det_lbl, const int* det_pos, const int* counts2, float alpha,
+                       float gamma, float* out, void* grad, double* slab, long R, int K, int dtype, hipStream_t s) {
+  const int nb = hnm_blocks(R);
+  sel_dtype(dtype, [&](auto tag) {
+    typedef decltype(tag) T;
+    sel_bool(grad != nullptr, [&](auto g) {
+      hipLaunchKernelGGL((focal_loss_kernel<T, decltype(g)::value>), dim3(nb), dim3(256), 0, s, (const T*)logits,
+                         det_lbl, det_pos, counts2, alpha, gamma, R, K, (T*)grad, slab);
+    });
+  });
+  hipLaunchKernelGGL(focal_finalize_kernel, dim3(1), dim3(256), 0, s, slab, nb, counts2, out);
+}
+
 }  // namespace rod
 
 using namespace rod;
@@ -608,6 +849,43 @@ int rod_hnm_loss(const void* logits, const int* det_lbl, const int* det_pos, con
     hipLaunchKernelGGL(hnm_finalize_kernel, dim3(1), dim3(256), 0, s, w.loss_slab, nb, state, bs, out);
   });
   return check_launch("rod_hnm_loss");
+}
+
+// ---- focal loss: the opt-in alternative to everything above (semantics: include/rod.h) ----
+size_t rod_softmax_focal_workspace(int B, int A) {
+  return 256 + (((size_t)hnm_blocks((long)B * A) * 2 * sizeof(double) + 255) & ~(size_t)255);
+}
+
+int rod_focal_count(const int* det_pos, void* workspace, int* counts2, int B, int A, void* stream) {
+  ROD_CHECK_ARG(B > 0 && A > 0, "rod_focal_count: B and A must be > 0 (got B %d, A %d)", B, A);
+  ROD_CHECK_ARG(det_pos && workspace && counts2, "rod_focal_count: det_pos/workspace/counts2 NULL");
+  if (int rc = focal_count(det_pos, counts2, (long)B * A, ROD_STREAM(stream))) return rc;
+  return check_launch("rod_focal_count");
+}
+
+int rod_focal_loss(const void* logits, const int* det_lbl, const int* det_pos, const int* counts2, float alpha,
+                   float gamma, float* out, void* grad, void* workspace, int B, int A, int K, int dtype,
+                   void* stream) {
+  if (int rc = focal_check("rod_focal_loss", B, A, K, alpha, gamma)) return rc;
+  ROD_CHECK_ARG(dtype == ROD_F32 || dtype == ROD_BF16, "rod_focal_loss: unsupported dtype code %d", dtype);
+  ROD_CHECK_ARG(logits && det_lbl && det_pos && counts2 && out && workspace,
+                "rod_focal_loss: logits/det_lbl/det_pos/counts2/out/workspace NULL");
+  focal_loss(logits, det_lbl, det_pos, counts2, alpha, gamma, out, grad, (double*)((char*)workspace + 256),
+             (long)B * A, K, dtype, ROD_STREAM(stream));
+  return check_launch("rod_focal_loss");
+}
+
+int rod_softmax_focal(const void* logits, const int* det_lbl, const int* det_pos, float alpha, float gamma,
+                      float* out, void* grad, void* workspace, int B, int A, int K, int dtype, void* stream) {
+  if (int rc = focal_check("rod_softmax_focal", B, A, K, alpha, gamma)) return rc;
+  ROD_CHECK_ARG(dtype == ROD_F32 || dtype == ROD_BF16, "rod_softmax_focal: unsupported dtype code %d", dtype);
+  ROD_CHECK_ARG(logits && det_lbl && det_pos && out && workspace,
+                "rod_softmax_focal: logits/det_lbl/det_pos/out/workspace NULL");
+  int* counts2 = (int*)workspace;
+  if (int rc = focal_count(det_pos, counts2, (long)B * A, ROD_STREAM(stream))) return rc;
+  focal_loss(logits, det_lbl, det_pos, counts2, alpha, gamma, out, grad, (double*)((char*)workspace + 256),
+             (long)B * A, K, dtype, ROD_STREAM(stream));
+  return check_launch("rod_softmax_focal");
 }
 
 }  // extern "C"

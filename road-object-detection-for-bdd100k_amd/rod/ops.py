@@ -1862,6 +1862,96 @@ def softmax_ce_hnm_dp(logits, det_lbl, det_pos, iou, lvl_off, bs, B_global, allr
     return _SoftmaxCEHNMDP.apply(logits, det_lbl, det_pos, iou, lvl_off, bs, B_global, allreduce)
 
 
+def _softmax_focal_raw(logits, det_lbl, det_pos, alpha, gamma, want_grad):
+    B, A, K = logits.shape
+    out = torch.empty(8, dtype=torch.float32, device=logits.device)
+    grad = torch.empty_like(logits, memory_format=torch.contiguous_format) if want_grad else None
+    ws = workspace(_abi.query("rod_softmax_focal_workspace", B, A), logits.device)
+    _abi.call("rod_softmax_focal", logits.contiguous(), det_lbl, det_pos, float(alpha), float(gamma), out, grad,
+              ws, B, A, K, dtcode(logits), stream())
+    return out, grad
+
+
+class _SoftmaxFocal(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, det_lbl, det_pos, alpha, gamma):
+        out, grad = _softmax_focal_raw(logits, det_lbl, det_pos, alpha, gamma, ctx.needs_input_grad[0])
+        ctx.save_for_backward(grad)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(out)
+        return out, out[2]
+
+    @staticmethod
+    def backward(ctx, g_vec, g_loss):
+        (grad,) = ctx.saved_tensors
+        # clf_loss enters the training loss with weight 1 (net_tools.det_clf_loss)
+        return (grad if g_loss is not None else None), None, None, None, None
+
+
+def softmax_focal(logits, det_lbl, det_pos, alpha, gamma):
+    """Focal loss of the ODM classifier (rod_softmax_focal; opt-in, replaces hard-negative mining
+    AND the IoU factor): ([8] pos_loss, neg_loss, clf_loss, 0, n_pos, 0, n_neg, norm; clf_loss as
+    a differentiable 0-d view).  The gradient is written by the forward launch, and only when it
+    can be asked for: logits requires grad and grad mode is on."""
+    if not (torch.is_grad_enabled() and logits.requires_grad):
+        out, _ = _softmax_focal_raw(logits, det_lbl, det_pos, alpha, gamma, False)
+        return out, out[2]
+    return _SoftmaxFocal.apply(logits, det_lbl, det_pos, alpha, gamma)
+
+
+def focal_lockstep(shards, alpha, gamma, allreduce, want_grad=True):
+    """softmax_focal over a batch split into shards, as hnm_lockstep: rod_focal_count for every
+    shard, ONE `allreduce(list_of_int32_tensors)` summing the (n_pos, n_neg) counts over all
+    shards in place, then rod_focal_loss for every shard with the global counts.  The counts are
+    integers, so norm and the gradient equal the single-call ones bit for bit.
+    shards: [(logits [B,A,K], det_lbl, det_pos)]; returns [(out [8], grad or None)]."""
+    st = []
+    for (logits, lbl, pos) in shards:
+        B, A, K = logits.shape
+        dev = logits.device
+        ws = workspace(_abi.query("rod_softmax_focal_workspace", B, A), dev)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        logits = logits.contiguous()
+        _abi.call("rod_focal_count", pos, ws, counts, B, A, stream())
+        st.append((logits, lbl, pos, ws, counts, B, A, K))
+    allreduce([x[4] for x in st])
+    res = []
+    for (logits, lbl, pos, ws, counts, B, A, K) in st:
+        out = torch.empty(8, dtype=torch.float32, device=logits.device)
+        grad = torch.empty_like(logits) if want_grad else None
+        _abi.call("rod_focal_loss", logits, lbl, pos, counts, float(alpha), float(gamma), out, grad, ws, B, A, K,
+                  dtcode(logits), stream())
+        res.append((out, grad))
+    return res
+
+
+class _SoftmaxFocalDP(torch.autograd.Function):
+    """softmax_focal for one data-parallel shard (focal_lockstep with the process group)."""
+
+    @staticmethod
+    def forward(ctx, logits, det_lbl, det_pos, alpha, gamma, allreduce):
+        ((out, grad),) = focal_lockstep([(logits, det_lbl, det_pos)], alpha, gamma, allreduce,
+                                        want_grad=ctx.needs_input_grad[0])
+        ctx.save_for_backward(grad)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(out)
+        return out, out[2]
+
+    @staticmethod
+    def backward(ctx, g_vec, g_loss):
+        (grad,) = ctx.saved_tensors
+        return (grad if g_loss is not None else None), None, None, None, None, None
+
+
+def softmax_focal_dp(logits, det_lbl, det_pos, alpha, gamma, allreduce):
+    """softmax_focal normalised by the positives of the GLOBAL batch of a data-parallel job
+    (allreduce: in-place SUM of a list of device int32 tensors over the ranks)."""
+    if not (torch.is_grad_enabled() and logits.requires_grad):
+        ((out, _),) = focal_lockstep([(logits, det_lbl, det_pos)], alpha, gamma, allreduce, want_grad=False)
+        return out, out[2]
+    return _SoftmaxFocalDP.apply(logits, det_lbl, det_pos, alpha, gamma, allreduce)
+
+
 def select_topk_nms(probs, boxes, select_threshold, top_k, keep_top_k, nms_threshold, compact=True):
     """rod_select_topk_nms.  compact: pass the candidate-list workspace (one row-wise pass over
     probs; used when select_threshold > 0) — False forces the direct column-wise kernel."""

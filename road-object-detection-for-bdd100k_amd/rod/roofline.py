@@ -226,6 +226,14 @@ def cost(name, a):
     if name == "rod_softmax":
         rows, K, dt = a[2], a[3], a[4]
         return rows * K * (_ES[dt] + 4), 4 * rows * K
+    if name in ("rod_softmax_focal", "rod_focal_loss"):
+        # logits read once, gradient written once, det_lbl + det_pos (+ det_pos again for the count)
+        off = 0 if name == "rod_softmax_focal" else 1
+        B, A, K, dt = a[8 + off], a[9 + off], a[10 + off], a[11 + off]
+        g = a[6 + off] is not None
+        return B * A * (K * _ES[dt] * (2 if g else 1) + (12 - 4 * off)), 60 * B * A * K
+    if name == "rod_focal_count":
+        return 4 * a[3] * a[4], a[3] * a[4]
     if name == "rod_select_topk_nms":
         B, A, K = a[2], a[3], a[4]
         return B * A * (K * 4 + 16), 0

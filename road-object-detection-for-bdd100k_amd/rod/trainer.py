@@ -13,6 +13,8 @@ bs, net_tools.py:513).  Clipping happens after the reduction (net_tools.py:649).
 BatchNorm statistics are per rank by default (documented deviation) or, with
 sync_bn=True, merged over the global batch (rod.ddp.SyncBatchNorm); the hard negatives are
 selected over the global batch (counts + radix histograms all-reduced, ops.hnm_lockstep).
+With clf_loss='focal' (opt-in) the classifier loss is the focal loss over every anchor instead,
+normalised by the positives of the global batch (one all-reduce of the counts, ops.focal_lockstep).
 """
 from __future__ import annotations
 
@@ -34,7 +36,8 @@ class Trainer:
                  deconv_method=config.deconv_method.LEARN_HALF, merge_method=config.merge_method.ADD,
                  sync_bn=False, backbone_name='mobilenet_v2',
                  process_backbone_method=config.process_backbone_method.NONE, momentum=0.0, nesterov=False,
-                 weight_decay=0.0, clip_norm=None, warmup_steps=0, fix_learning_rate=True):
+                 weight_decay=0.0, clip_norm=None, warmup_steps=0, fix_learning_rate=True, clf_loss='hnm',
+                 focal_alpha=0.25, focal_gamma=2.0):
         self.img_size = tuple(img_size)
         self.batch_size = batch_size          # per-rank batch
         self.world_size = world_size
@@ -72,6 +75,10 @@ class Trainer:
             if dp and hasattr(reducer, 'hnm_allreduce') else None
         self.train_range = train_range
         self.fix_refine = fix_refine
+        # the ODM classifier loss: the reference's hard-negative mining, or (opt-in) focal loss
+        if clf_loss not in ('hnm', 'focal'):
+            raise ValueError("clf_loss must be 'hnm' or 'focal', got %r" % (clf_loss,))
+        self.clf_loss, self.focal_alpha, self.focal_gamma = clf_loss, float(focal_alpha), float(focal_gamma)
         # BatchNorm over the global batch (opt-in; per-rank statistics otherwise)
         self.sync_bn = bool(sync_bn and (world_size > 1 or dp))
         if self.sync_bn:
@@ -123,6 +130,7 @@ class Trainer:
             return 'eager'
         if self.reducer is None or getattr(self.reducer, 'native', False):
             return 'full'
+        # (focal loss keeps one mid-step collective, the positive count: the same rule)
         hnm = self.train_range is not config.train_range.REFINE and net_tools.HNM_EXCHANGE is not None
         mid = self.sync_bn or hnm
         return 'eager' if mid or not hasattr(self.reducer, 'defer') else 'split'
@@ -219,7 +227,8 @@ class Trainer:
             dgt = net_tools.det_groundtruth(refine_out, tg[0], tg[1], tg[2], tg[3], self.anchors, targets=tg,
                                             refine_flat=rflat[1])
             d_loss, c_loss = net_tools.det_clf_loss(refine_out, clf_out, det_out, dgt, dgt[1], dgt[2], dgt[3],
-                                                    scale=scale)
+                                                    scale=scale, clf_loss=self.clf_loss,
+                                                    focal_alpha=self.focal_alpha, focal_gamma=self.focal_gamma)
             loss = graph.scalar_sum(d_loss, c_loss) if self.fix_refine else graph.scalar_sum(r_loss, d_loss, c_loss)
             losses = (loss, r_loss, d_loss, c_loss)
             self.last_targets = (tg, dgt)

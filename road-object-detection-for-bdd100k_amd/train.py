@@ -15,6 +15,9 @@ Optimiser: by default the reference's (plain SGD, clip by value +-5, constant ra
 norm), --warmup_steps (linear) and --fix_learning_rate=False (the 0.97 staircase the reference
 only logs becomes the applied rate); any of them selects the momentum-SGD kernel, under
 --hip_graph too.  The summary record's `lr` is the rate the step applied.
+
+Classifier loss (--train_range ALL): by default the reference's (hard-negative mining, IoU factor).
+--clf_loss focal replaces both by focal loss (--focal_alpha 0.25, --focal_gamma 2.0).
 """
 import argparse
 import json
@@ -89,7 +92,31 @@ def parse(argv=None):
     ap.add_argument('--fix_learning_rate', type=str2bool, default=True,
                     help='False: apply the exponential staircase decay (0.97 every 20000 / batch_size steps) '
                          'that the reference only logs')
-    return ap.parse_args(argv)
+    # classifier-loss addition (neutral by default: the reference's hard-negative mining + IoU factor)
+    ap.add_argument('--clf_loss', default='hnm', choices=['hnm', 'focal'],
+                    help="ODM classifier loss (--train_range ALL): 'hnm' = softmax cross-entropy with 3:1 hard-negative "
+                         "mining and the IoU factor (the reference); 'focal' = focal loss over every anchor, "
+                         'normalised by the positives, in place of both')
+    ap.add_argument('--focal_alpha', type=float, default=None,
+                    help='focal loss: weight of the positives, 1 - alpha on the negatives; in [0, 1] (default 0.25)')
+    ap.add_argument('--focal_gamma', type=float, default=None,
+                    help='focal loss: focusing exponent, finite and >= 0 (default 2.0)')
+    F = ap.parse_args(argv)
+    given = [n for n in ('focal_alpha', 'focal_gamma') if getattr(F, n) is not None]
+    if F.focal_alpha is None:
+        F.focal_alpha = 0.25
+    if F.focal_gamma is None:
+        F.focal_gamma = 2.0
+    if not 0.0 <= F.focal_alpha <= 1.0:       # (a NaN fails both comparisons)
+        ap.error('--focal_alpha must be in [0, 1], got %r' % F.focal_alpha)
+    if not (0.0 <= F.focal_gamma < float('inf')):
+        ap.error('--focal_gamma must be finite and >= 0, got %r' % F.focal_gamma)
+    if F.train_range == 'REFINE' and (F.clf_loss != 'hnm' or given):
+        ap.error('--clf_loss focal / --focal_alpha / --focal_gamma need --train_range ALL: REFINE training has no '
+                 'classifier loss to apply them to')
+    if F.clf_loss == 'hnm' and given:
+        ap.error('--%s needs --clf_loss focal' % given[0])
+    return F
 
 
 def load_ckpt(store, path, names_regex=None, optimizer=None):
@@ -190,7 +217,12 @@ def main(argv=None):
                       device=dev, fix_refine=F.fix_refine, seed=F.seed, world_size=world,
                       reducer=make_reducer(world, rank) if world > 1 else None, backbone_name=F.backbone_name,
                       sync_bn=F.sync_bn, momentum=F.momentum, nesterov=F.nesterov, weight_decay=F.weight_decay,
-                      clip_norm=F.clip_norm, warmup_steps=F.warmup_steps, fix_learning_rate=F.fix_learning_rate)
+                      clip_norm=F.clip_norm, warmup_steps=F.warmup_steps, fix_learning_rate=F.fix_learning_rate,
+                      clf_loss=F.clf_loss, focal_alpha=F.focal_alpha, focal_gamma=F.focal_gamma)
+    if tr_range is config.train_range.ALL:
+        logger.info('Classifier loss: %s' % ('focal loss, alpha=%g gamma=%g (no hard-negative mining, no IoU factor)'
+                                              % (F.focal_alpha, F.focal_gamma) if F.clf_loss == 'focal'
+                                              else 'softmax cross-entropy with 3:1 hard-negative mining'))
     store = trainer.net.store
     logger.info('Total trainable parameters:%s' % str(store.trainable_count()))
     step0 = 0

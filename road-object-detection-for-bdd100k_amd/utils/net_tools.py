@@ -363,13 +363,22 @@ HNM_EXCHANGE = None
 
 
 def det_clf_loss(refine_out, clf_out, det_out, det_groundtruth, det_pos_mask, det_labels, iou_all_layers,
-                 dtype=torch.float32, scale=None, targets=None):
+                 dtype=torch.float32, scale=None, targets=None, clf_loss='hnm', focal_alpha=0.25, focal_gamma=2.0):
     """(det_loss, clf_loss) (net_tools.py:519-623): masked smooth-L1 on the ODM offsets and
     softmax cross-entropy with global hard-negative mining and the IoU focal factor.
+
+    clf_loss='focal' (opt-in; the reference has none) replaces BOTH the hard-negative mining and
+    the IoU factor by the focal loss of Lin et al. 2017 over every anchor, normalised by the
+    number of positives of the global batch (rod_softmax_focal; focal_alpha weighs the positives,
+    1 - focal_alpha the negatives).  The classifier loss then does not depend on the IoU: no
+    gradient reaches refine_out through it.  last_stats is then [pos_loss, neg_loss, clf_loss, 0,
+    n_pos, 0, n_neg, norm].  The smooth-L1 loss is the same in both modes.
 
     `det_groundtruth` may be the object returned by det_groundtruth() (fast path).  The
     summaries the reference logs (pos/neg/clf loss, max hard prediction, positives) are
     left in det_clf_loss.last_stats ([8] device tensor, see rod_softmax_ce_hnm)."""
+    if clf_loss not in ('hnm', 'focal'):
+        raise ValueError("clf_loss must be 'hnm' or 'focal', got %r" % (clf_loss,))
     B = clf_out[0].shape[0]
     scale = float(B) if scale is None else float(scale)
     tg = det_groundtruth if isinstance(det_groundtruth, RefineTargets) and hasattr(det_groundtruth, 'flat') \
@@ -381,7 +390,12 @@ def det_clf_loss(refine_out, clf_out, det_out, det_groundtruth, det_pos_mask, de
     pred = ops.levels_concat(det_out, 4)
     dvec, det_loss_one = ops.smooth_l1_masked(pred, det_gt, det_pos, lvl_off, scale)
     logits = ops.levels_concat(clf_out, config.total_obj_n)
-    if HNM_EXCHANGE is not None:   # data parallel: hard negatives over the global batch (§8e)
+    if clf_loss == 'focal':        # data parallel: the positives of the global batch
+        if HNM_EXCHANGE is not None:
+            cvec, clf_loss = ops.softmax_focal_dp(logits, det_lbl, det_pos, focal_alpha, focal_gamma, HNM_EXCHANGE[0])
+        else:
+            cvec, clf_loss = ops.softmax_focal(logits, det_lbl, det_pos, focal_alpha, focal_gamma)
+    elif HNM_EXCHANGE is not None:   # data parallel: hard negatives over the global batch (§8e)
         allreduce, world = HNM_EXCHANGE
         cvec, clf_loss = ops.softmax_ce_hnm_dp(logits, det_lbl, det_pos, iou, lvl_off, scale, B * world, allreduce)
     else:
