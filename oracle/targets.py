@@ -121,6 +121,69 @@ def refine_groundtruth_nn(anchors_all, center_bboxes, labels):
     return gt_l, cb_l, lb_l, pm_l
 
 
+def encode_flat(anc_center, cbox):
+    """encode against an [A, 4] table of anchor centres (cy, cx, h, w)."""
+    ac = np.asarray(anc_center, np.float32)
+    with np.errstate(all='ignore'):
+        return np.stack([(f32(cbox[0]) - ac[:, 0]) / ac[:, 2], (f32(cbox[1]) - ac[:, 1]) / ac[:, 3],
+                         log_cr(f32(cbox[2]) / ac[:, 2]), log_cr(f32(cbox[3]) / ac[:, 3])], -1)
+
+
+def _level_of(lvl_off, A):
+    return np.searchsorted(np.asarray(lvl_off[1:-1]), np.arange(A), side='right')
+
+
+def refine_groundtruth_flat(anc_corner, anc_center, lvl_off, thr, center_bboxes, labels):
+    """refine_groundtruth on flat [A, 4] tables (corner and centre form of the same anchors)
+    with level offsets lvl_off [L + 1] and thresholds thr [L], ONE image: the same float32
+    operations in the same order, returns (off [A, 4], cbox [A, 4], lbl [A], pos [A]); all
+    zeros for zero boxes."""
+    corners = np.asarray(anc_corner, np.float32)
+    cb = np.asarray(center_bboxes, np.float32).reshape(-1, 4)
+    lab = np.asarray(labels).reshape(-1)
+    A = corners.shape[0]
+    gt = np.zeros((A, 4), np.float32)
+    cbox = np.zeros((A, 4), np.float32)
+    lbl = np.zeros((A, 1), np.int32)
+    if cb.shape[0] == 0:
+        return gt, cbox, lbl[:, 0], np.zeros(A, np.int32)
+    t = np.asarray(thr, np.float32)[_level_of(lvl_off, A)]
+    with np.errstate(all='ignore'):
+        jac = np.stack([jaccard(corners, center_to_corner(cb[i])) for i in range(cb.shape[0])], 0)
+        pos = (jac.max(0) >= t).astype(np.int32)[..., None]
+        idx = jac.argmax(0)
+        for i in range(cb.shape[0]):
+            mask = (idx == i).astype(np.float32)[..., None] * pos.astype(np.float32)
+            cbox = cbox + mask * cb[i]
+            gt = gt + mask * encode_flat(anc_center, cb[i])
+            lbl = lbl + mask.astype(np.int32) * np.int32(lab[i])
+    return gt, cbox, lbl[:, 0], pos[:, 0]
+
+
+def refine_groundtruth_nn_flat(anc_corner, anc_center, lvl_off, thr, center_bboxes, labels):
+    """refine_groundtruth_nn on flat tables (anc_corner, lvl_off and thr are not used: the
+    signature is that of refine_groundtruth_flat), ONE image; all zeros for zero boxes."""
+    cb = np.asarray(center_bboxes, np.float32).reshape(-1, 4)
+    lab = np.asarray(labels).reshape(-1)
+    A = np.asarray(anc_center).shape[0]
+    gt = np.zeros((A, 4), np.float32)
+    cbox = np.zeros((A, 4), np.float32)
+    lbl = np.zeros((A, 1), np.int32)
+    if cb.shape[0] == 0:
+        return gt, cbox, lbl[:, 0], np.zeros(A, np.int32)
+    with np.errstate(all='ignore'):
+        loc = np.stack([encode_flat(anc_center, cb[i]) for i in range(cb.shape[0])], 0)   # [G, A, 4]
+        sq = loc * loc
+        dist = ((sq[..., 0] + sq[..., 1]) + sq[..., 2]) + sq[..., 3]
+        idx = dist.argmin(0)
+        for i in range(cb.shape[0]):
+            mask = (idx == i).astype(np.float32)[..., None]
+            cbox = cbox + mask * cb[i]
+            gt = gt + mask * loc[i]
+            lbl = lbl + mask.astype(np.int32) * np.int32(lab[i])
+    return gt, cbox, lbl[:, 0], np.ones(A, np.int32)
+
+
 def smooth_l1(x):
     """net_tools.py:478-489."""
     x = np.asarray(x, np.float32)
