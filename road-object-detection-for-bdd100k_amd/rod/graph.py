@@ -75,4 +75,4 @@ def backward(loss):
         left = clear_bn_parts()   # BatchNorm sums / gradient recipes handed between nodes live for one backward
     if ok and left:
         raise RuntimeError("%d unmaterialised depthwise-input gradient(s) reached a node other than their "
-                           "depthwise (rod.ops._DZ_RECIPE)" % left)
+                           "depthwise (the rod.ops._DZ_RECIPE hand-off)" % left)

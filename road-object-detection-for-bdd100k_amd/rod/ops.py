@@ -313,6 +313,11 @@ def _sync_nparts(M):
     return int(max(1, min(1024, M // 256)))
 
 
+def _conv_stat_parts(M, Cout, device):
+    """The BatchNorm partial statistics a conv's epilogue writes: [ceil(M/128)][3][Cout]."""
+    return torch.empty((-(-M // 128), 3, Cout), dtype=torch.float32, device=device)
+
+
 # ----------------------------------------------------------------------------- BatchNorm prologue
 class Pending:
     """act(BatchNorm(y)) whose statistics are known but which is NOT materialised.
@@ -363,6 +368,40 @@ def _bn_backward(dz, y, mean, rstd, gamma, beta, act, need_g, need_b):
     return dy
 
 
+class _HandOff:
+    """Payloads handed from one backward node to another, keyed by the gradient tensor that
+    travels between them.  An entry holds its tensor (so the memory cannot be reused while
+    listed) and is accepted only for that very tensor, or a view of the same storage with the
+    same shape and dtype, and only while the version counter is unchanged.  take() pops the
+    entry either way; a mismatch gives None, or raises when strict."""
+
+    def __init__(self, what):
+        self.what = what
+        self.entries = {}
+
+    def put(self, t, payload):
+        self.entries[t.data_ptr()] = (t, payload, t._version)
+
+    def take(self, t, strict=False):
+        e = self.entries.pop(t.data_ptr(), None) if t is not None else None
+        if e is None:
+            return None
+        src, payload, ver = e
+        same = src is t or (src.shape == t.shape and src.dtype == t.dtype and
+                            src.untyped_storage().data_ptr() == t.untyped_storage().data_ptr())
+        if same and t._version == ver:
+            return payload
+        if strict:
+            raise RuntimeError("%s was modified or aliased before its consumer took it" % self.what)
+        return None
+
+    def clear(self):
+        """Drop every entry; returns how many were never taken."""
+        left = len(self.entries)
+        self.entries.clear()
+        return left
+
+
 # BatchNorm-backward sums handed from a consumer's backward to the producer's.  Two families of
 # kernels produce them: the fused depthwise backwards (rod_dw3x3_bwd_fused / _fused_pw /
 # _fused_rc, in _DWBN.backward) and the fused project / 16 -> 96 expand backwards
@@ -370,39 +409,21 @@ def _bn_backward(dz, y, mean, rstd, gamma, beta, act, need_g, need_b):
 # gradient dx it returns for its input act(BN(y)), that BatchNorm's backward sums over (dx, y).
 # The producer node (_ConvBN after a depthwise, _DWBN or the previous block's _ConvBN after a
 # 1x1 conv) receives exactly that dx as its dz when the kernel's node is the only consumer, and
-# then finalizes the sums instead of running rod_bn_bwd_reduce over (dz, y).  Entries hold their
-# dx (so its memory cannot be reused while listed) and are dropped when the backward ends.
-# An entry is accepted only for the very tensor it was made for, or a view of the same storage
-# whose version counter is unchanged: a gradient summed IN PLACE into dx (a second consumer of
-# the depthwise input) shares dx's pointer and shape but bumps its version, and then the
-# producer runs its own reduce over the summed dz instead of picking up stale sums.
-_BN_PARTS = {}
-
-
-def _put_bn_parts(dx, parts):
-    _BN_PARTS[dx.data_ptr()] = (dx, parts, dx._version)
-
-
-def _take_bn_parts(dz):
-    e = _BN_PARTS.pop(dz.data_ptr(), None) if dz is not None else None
-    if e is None:
-        return None
-    dx, parts, ver = e
-    if dx is dz:
-        return parts if dz._version == ver else None
-    if dx.shape != dz.shape or dx.dtype != dz.dtype or dz._version != ver or \
-            dx.untyped_storage().data_ptr() != dz.untyped_storage().data_ptr():
-        return None
-    return parts
+# then finalizes the sums instead of running rod_bn_bwd_reduce over (dz, y).  Entries are
+# dropped when the backward ends.  A mismatch is not an error here: a gradient summed IN PLACE
+# into dx (a second consumer of the depthwise input) shares dx's pointer and shape but bumps
+# its version, and then the producer runs its own reduce over the summed dz instead of picking
+# up stale sums.
+_BN_PARTS = _HandOff("a BatchNorm-backward sum")
+_put_bn_parts = _BN_PARTS.put
+_take_bn_parts = _BN_PARTS.take
 
 
 def clear_bn_parts():
     """End of a backward: drop the hand-offs.  Returns how many unmaterialised depthwise-input
     gradients (the project recipes below) were never consumed by their depthwise node."""
     _BN_PARTS.clear()
-    left = len(_DZ_RECIPE)
-    _DZ_RECIPE.clear()
-    return left
+    return _DZ_RECIPE.clear()
 
 
 # Unmaterialised depthwise-output gradients (ABI 20).  In an inverted-residual block the gradient
@@ -411,26 +432,8 @@ def clear_bn_parts():
 # placeholder of dz's shape whose memory is never written.  The depthwise node takes the recipe
 # (rod_dw3x3_bwd_fused_pw recomputes dz per tile, or rod_conv_fwd materialises it for any other
 # path); a placeholder that reaches anything else is caught at the end of backward (graph.backward).
-_DZ_RECIPE = {}
-
-
-def _put_dz_recipe(dz, recipe):
-    _DZ_RECIPE[dz.data_ptr()] = (dz, recipe, dz._version)
-
-
-def _take_dz_recipe(dz):
-    if dz is None:
-        return None
-    e = _DZ_RECIPE.pop(dz.data_ptr(), None)
-    if e is None:
-        return None
-    ph, recipe, ver = e
-    same = ph is dz or (ph.shape == dz.shape and ph.dtype == dz.dtype and
-                        ph.untyped_storage().data_ptr() == dz.untyped_storage().data_ptr())
-    if not same or dz._version != ver:
-        raise RuntimeError("an unmaterialised depthwise-input gradient was modified or aliased before its "
-                           "depthwise node consumed it")
-    return recipe
+# A recipe is taken strictly: a placeholder that was modified or aliased on the way raises.
+_DZ_RECIPE = _HandOff("an unmaterialised depthwise-input gradient")
 
 
 def _materialize_dz(recipe, shape, dtype):
@@ -444,14 +447,15 @@ def _materialize_dz(recipe, shape, dtype):
 
 
 def bn_bwd_coef_from_parts(parts, M, C, rstd, gamma, beta, need_g, need_b):
-    """rod_bn_bwd_finalize of [nparts][2][C] backward sums (a consumer kernel's epilogue) ->
-    coef [3, C]; dgamma / dbeta to the parameters' slots.  Under SyncBatchNorm the parts are
-    all-gathered first (the parameter gradients stay this rank's own sums, as bn_bwd_reduce)."""
+    """rod_bn_bwd_finalize of [nparts][2][C] backward sums (a consumer kernel's epilogue, or
+    rod_bn_bwd_parts) -> coef [3, C]; dgamma / dbeta to the parameters' slots.  Under
+    SyncBatchNorm the parts are all-gathered first."""
     coef = torch.empty(3 * C, dtype=torch.float32, device=parts.device)
     dg, db = _bn_grad_slots(gamma, beta, need_g, need_b)
     nparts = parts.shape[0]
     if SYNC_BN is not None:
         if dg is not None or db is not None:
+            # parameter gradients from this rank's rows only: the DP reducer sums them
             _abi.call("rod_bn_bwd_finalize", parts, nparts, M, C, rstd, gamma, dg, db,
                       torch.empty(3 * C, dtype=torch.float32, device=parts.device), stream())
         gp = SYNC_BN.gather(parts)
@@ -468,24 +472,16 @@ def bn_bwd_reduce(dz, y, mean, rstd, gamma, beta, act, need_g, need_b):
     that applies dy itself; dgamma / dbeta go to the parameters' flat-buffer slots."""
     C = y.shape[-1]
     M = y.numel() // C
-    coef = torch.empty(3 * C, dtype=torch.float32, device=y.device)
-    dg, db = _bn_grad_slots(gamma, beta, need_g, need_b)
-    if SYNC_BN is not None:
-        dz = dz.contiguous()
+    if SYNC_BN is not None:   # this rank's sums as parts, merged over the ranks
         nparts = _sync_nparts(M)
         parts = torch.empty((nparts, 2, C), dtype=torch.float32, device=y.device)
-        _abi.call("rod_bn_bwd_parts", dz, y, mean, rstd, gamma, beta, act, parts, nparts, M, C, dtcode(y), stream())
-        if dg is not None or db is not None:
-            # parameter gradients from this rank's rows only: the DP reducer sums them
-            _abi.call("rod_bn_bwd_finalize", parts, nparts, M, C, rstd, gamma, dg, db,
-                      torch.empty(3 * C, dtype=torch.float32, device=y.device), stream())
-        gp = SYNC_BN.gather(parts)
-        _abi.call("rod_bn_bwd_finalize", gp, gp.shape[0], M * SYNC_BN.world, C, rstd, gamma, None, None, coef,
-                  stream())
-    else:
-        ws = workspace(_abi.query("rod_bn_bwd_workspace", M, C), y.device)
-        _abi.call("rod_bn_bwd_reduce", dz, y, mean, rstd, gamma, beta, dg, db, coef, ws, M, C, act, dtcode(y),
-                  stream())
+        _abi.call("rod_bn_bwd_parts", dz.contiguous(), y, mean, rstd, gamma, beta, act, parts, nparts, M, C,
+                  dtcode(y), stream())
+        return bn_bwd_coef_from_parts(parts, M, C, rstd, gamma, beta, need_g, need_b)
+    coef = torch.empty(3 * C, dtype=torch.float32, device=y.device)
+    dg, db = _bn_grad_slots(gamma, beta, need_g, need_b)
+    ws = workspace(_abi.query("rod_bn_bwd_workspace", M, C), y.device)
+    _abi.call("rod_bn_bwd_reduce", dz, y, mean, rstd, gamma, beta, dg, db, coef, ws, M, C, act, dtcode(y), stream())
     _bn_grads_written(gamma, beta, need_g, need_b)
     return coef
 
@@ -646,6 +642,21 @@ def _split_in(x):
 
 
 # ----------------------------------------------------------------------------- depthwise
+def _dw_bwd_data(dy, w, x, geo):
+    """rod_dw3x3_bwd_data: the gradient wrt the depthwise input x; geo as ctx.geo."""
+    dx = torch.empty_like(x)
+    _abi.call("rod_dw3x3_bwd_data", dy, w, dx, *_gred_args(None), *geo, dtcode(x), stream())
+    return dx
+
+
+def _dw_bwd_filter(x, pro, dy, w, geo):
+    """rod_dw3x3_bwd_filter: the filter gradient into w's flat-buffer slot; geo as ctx.geo."""
+    N, _, _, C, _, _, _, Ho, Wo = geo
+    ws = workspace(_abi.query("rod_dw3x3_bwd_filter_workspace", N, Ho, Wo, C), x.device)
+    _abi.call("rod_dw3x3_bwd_filter", x, *_pro_args(pro), dy, grad_slot(w), ws, *geo, dtcode(x), stream())
+    _mark_written(w)
+
+
 class _DW3x3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, stride, want_stats, gamma, beta, mean, rstd, act, training, owned=False):
@@ -673,7 +684,6 @@ class _DW3x3(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, *_):
         x, w, gamma, beta, mean, rstd = ctx.saved_tensors
-        N, H, W, C, s, pt, pl, Ho, Wo = ctx.geo
         dy = dy.contiguous()
         pro = (mean, rstd, gamma, beta, ctx.act) if ctx.pro else None
         need_g = ctx.pro and gamma is not None and ctx.needs_input_grad[4]
@@ -682,15 +692,9 @@ class _DW3x3(torch.autograd.Function):
         if ctx.needs_input_grad[0] or need_g or need_b:
             if ctx.pro and not ctx.training:
                 raise RuntimeError("BatchNorm backward in inference mode is not part of the reference graph")
-            dx = torch.empty_like(x)   # gradient wrt the dw input (the BatchNorm output when pro)
-            _abi.call("rod_dw3x3_bwd_data", dy, w, dx, *_gred_args(None), N, H, W, C, s, pt, pl, Ho, Wo, dtcode(x),
-                      stream())
+            dx = _dw_bwd_data(dy, w, x, ctx.geo)   # gradient wrt the dw input (the BatchNorm output when pro)
         if ctx.needs_input_grad[1]:
-            g = grad_slot(w)
-            ws = workspace(_abi.query("rod_dw3x3_bwd_filter_workspace", N, Ho, Wo, C), x.device)
-            _abi.call("rod_dw3x3_bwd_filter", x, *_pro_args(pro), dy, g, ws, N, H, W, C, s, pt, pl, Ho, Wo,
-                      dtcode(x), stream())
-            _mark_written(w)
+            _dw_bwd_filter(x, pro, dy, w, ctx.geo)
         if ctx.pro and dx is not None and not ctx.owned:
             dx = _bn_backward(dx, x, mean, rstd, gamma, beta, ctx.act, need_g, need_b)
         return dx, None, None, None, None, None, None, None, None, None, None
@@ -733,6 +737,23 @@ def conv_fwd_raw(x, wt, b, y, N, H, W, Cin, Cout, ksize, stat_parts=None, pro=No
               ksize, 0, 0, dtcode(x), stream())
 
 
+def _conv_wgrad(x, pro, dy, w, b, need_w, need_bias, geo):
+    """rod_conv_wgrad: dw / db of a dense conv into the parameters' flat-buffer slots, where
+    needed; geo = (N, H, W, Cin, Cout, ksize) of the GEMM (x may be a column matrix)."""
+    if not (need_w or need_bias):
+        return
+    gw = grad_slot(w) if need_w else None
+    if gw is None:  # the kernel always writes dW: a scratch one for a bias-only gradient or a weight without a slot
+        gw = torch.empty(w.shape, dtype=torch.float32, device=x.device)
+    gb = grad_slot(b) if need_bias else None
+    ws = workspace(_abi.query("rod_conv_wgrad_workspace", *geo), x.device)
+    _abi.call("rod_conv_wgrad", x, *_pro_args(pro), dy, gw, gb, ws, *geo, 0, 0, dtcode(x), stream())
+    if need_w:
+        _mark_written(w)
+    if need_bias:
+        _mark_written(b)
+
+
 class _Conv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, ksize, want_stats, gamma, beta, mean, rstd, act, training, owned=False):
@@ -743,8 +764,8 @@ class _Conv(torch.autograd.Function):
         wt = _prep(w, 0, x.dtype, Cout, Cin, ksize)
         y = torch.empty((N, H, W, Cout), dtype=x.dtype, device=x.device)
         parts = None
-        if want_stats:  # BatchNorm partial statistics from the epilogue ([ceil(M/128)][3][Cout])
-            parts = torch.empty((-(-(N * H * W) // 128), 3, Cout), dtype=torch.float32, device=x.device)
+        if want_stats:  # BatchNorm partial statistics from the epilogue
+            parts = _conv_stat_parts(N * H * W, Cout, x.device)
         pro = (mean, rstd, gamma, beta, act) if mean is not None else None
         conv_fwd_raw(x, wt, b, y, N, H, W, Cin, Cout, ksize, parts, pro)
         ctx.save_for_backward(x, w, b, gamma, beta, mean, rstd)
@@ -773,20 +794,8 @@ class _Conv(torch.autograd.Function):
             wt1 = _prep(w, 1, x.dtype, Cout, Cin, ks)
             dx = torch.empty_like(x)   # gradient wrt the conv input (the BatchNorm output when pro)
             conv_fwd_raw(dy, wt1, None, dx, N, H, W, Cout, Cin, ks)
-        need_w = ctx.needs_input_grad[1]
-        need_bias = b is not None and ctx.needs_input_grad[2]
-        if need_w or need_bias:
-            gw = grad_slot(w) if need_w else None
-            if gw is None:  # bias-only gradient still needs a scratch dW
-                gw = torch.empty(w.shape, dtype=torch.float32, device=x.device)
-            gb = grad_slot(b) if need_bias else None
-            ws = workspace(_abi.query("rod_conv_wgrad_workspace", N, H, W, Cin, Cout, ks), x.device)
-            _abi.call("rod_conv_wgrad", x, *_pro_args(pro), dy, gw, gb, ws, N, H, W, Cin, Cout, ks, 0, 0, dtcode(x),
-                      stream())
-            if need_w:
-                _mark_written(w)
-            if need_bias:
-                _mark_written(b)
+        _conv_wgrad(x, pro, dy, w, b, ctx.needs_input_grad[1], b is not None and ctx.needs_input_grad[2],
+                    (N, H, W, Cin, Cout, ks))
         if ctx.pro and dx is not None and not ctx.owned:
             dx = _bn_backward(dx, x, mean, rstd, gamma, beta, ctx.act, need_g, need_b)
         return dx, None, None, None, None, None, None, None, None, None, None, None
@@ -810,6 +819,11 @@ def bn_statistics(x, mmean, mvar, training, decay, eps=1e-3, parts=None):
     M = x.numel() // C
     mean = torch.empty(C, dtype=torch.float32, device=x.device)
     rstd = torch.empty(C, dtype=torch.float32, device=x.device)
+
+    def finalize(parts, rows):   # rod_bn_finalize of [nparts][3][C] partial statistics over `rows` rows
+        nb = _abi.query("rod_bn_finalize_workspace", parts.shape[0], C)
+        ws = workspace(nb, x.device) if nb else None
+        _abi.call("rod_bn_finalize", parts, parts.shape[0], rows, C, eps, decay, mean, rstd, mmean, mvar, ws, stream())
     if "epistats" in _DISABLE:
         parts = None
     if training and SYNC_BN is not None:   # statistics over the global batch (all ranks' parts)
@@ -817,15 +831,9 @@ def bn_statistics(x, mmean, mvar, training, decay, eps=1e-3, parts=None):
             nparts = _sync_nparts(M)
             parts = torch.empty((nparts, 3, C), dtype=torch.float32, device=x.device)
             _abi.call("rod_bn_stat_parts", x.contiguous(), M, C, parts, nparts, dtcode(x), stream())
-        gp = SYNC_BN.gather(parts)
-        nb = _abi.query("rod_bn_finalize_workspace", gp.shape[0], C)
-        ws = workspace(nb, x.device) if nb else None
-        _abi.call("rod_bn_finalize", gp, gp.shape[0], M * SYNC_BN.world, C, eps, decay, mean, rstd, mmean, mvar, ws,
-                  stream())
+        finalize(SYNC_BN.gather(parts), M * SYNC_BN.world)
     elif training and parts is not None:  # statistics already reduced by the producer's epilogue
-        nb = _abi.query("rod_bn_finalize_workspace", parts.shape[0], C)
-        ws = workspace(nb, x.device) if nb else None
-        _abi.call("rod_bn_finalize", parts, parts.shape[0], M, C, eps, decay, mean, rstd, mmean, mvar, ws, stream())
+        finalize(parts, M)
     elif training:
         ws = workspace(_abi.query("rod_bn_stats_workspace", M, C), x.device)
         _abi.call("rod_bn_stats", x, M, C, 0, eps, decay, mean, rstd, mmean, mvar, ws, dtcode(x), stream())
@@ -837,14 +845,20 @@ def bn_statistics(x, mmean, mvar, training, decay, eps=1e-3, parts=None):
     return mean, rstd
 
 
+def _bn_apply_raw(x, pro, residual, out, ldo=0):
+    """rod_bn_apply: out = act(BN(x)) (+ residual after the activation), pro = (mean, rstd, gamma,
+    beta, act); ldo = the row stride of out in elements when it is wider than x (0: dense)."""
+    mean, rstd, gamma, beta, act = pro
+    C = x.shape[-1]
+    _abi.call("rod_bn_apply", x, mean, rstd, gamma, beta, residual, out, x.numel() // C, C, 0, 0, ldo, act,
+              dtcode(x), stream())
+    return out
+
+
 class _BNAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, residual, mean, rstd, act, training):
-        N, H, W, C = x.shape
-        M = N * H * W
-        y = torch.empty_like(x)
-        _abi.call("rod_bn_apply", x, mean, rstd, gamma, beta, residual, y, M, C, 0, 0, 0, act, dtcode(x),
-                  stream())
+        y = _bn_apply_raw(x, (mean, rstd, gamma, beta, act), residual, torch.empty_like(x))
         ctx.save_for_backward(x, mean, rstd, gamma, beta)
         ctx.act = act
         ctx.training = training
@@ -927,6 +941,15 @@ def bn_bwd_dy(dz, y, mean, rstd, gamma, beta, act, need_g, need_b):
     return _bn_bwd_apply(dz, y, mean, rstd, gamma, beta, act, coef)
 
 
+def _bn_bwd_dy_owned(parts, dz, y, mean, rstd, gamma, beta, act):
+    """d/dy of an owned BatchNorm, written out: the coefficients from the sums a consumer's
+    backward handed over (parts) and the apply, else bn_bwd_dy over (dz, y)."""
+    if parts is not None:
+        coef = _bn_bwd_coef(parts, dz, y, mean, rstd, gamma, beta, act)
+        return _bn_bwd_apply(dz, y, mean, rstd, gamma, beta, act, coef)
+    return bn_bwd_dy(dz, y, mean, rstd, gamma, beta, act, _needs(gamma), _needs(beta))
+
+
 # fused 1x1 backward where it measured faster than the unfused chain (tools/pwbwd_bench.py):
 # the expand-shaped convs (Cout >= 2 Cin) on >= 200k rows
 def _pw_fused_ok(M, Cin, Cout, dtype):
@@ -960,23 +983,28 @@ def _conv_bwd_from_dy(x, w, b, ks, dy, pro, need_dx):
     """rod_conv_wgrad for dw / db and rod_conv_fwd (mode-1 weights) for dx from a dense dy."""
     N, H, W, Cin = x.shape
     Cout = w.shape[0]
-    need_w, need_bias = _needs(w), _needs(b)
-    if need_w or need_bias:
-        gw = grad_slot(w) if need_w else torch.empty(w.shape, dtype=torch.float32, device=x.device)
-        gb = grad_slot(b) if need_bias else None
-        ws = workspace(_abi.query("rod_conv_wgrad_workspace", N, H, W, Cin, Cout, ks), x.device)
-        _abi.call("rod_conv_wgrad", x, *_pro_args(pro), dy, gw, gb, ws, N, H, W, Cin, Cout, ks, 0, 0,
-                  dtcode(x), stream())
-        if need_w:
-            _mark_written(w)
-        if need_bias:
-            _mark_written(b)
+    _conv_wgrad(x, pro, dy, w, b, _needs(w), _needs(b), (N, H, W, Cin, Cout, ks))
     dx = None
     if need_dx:
         wt1 = _prep(w, 1, x.dtype, Cout, Cin, ks)
         dx = torch.empty_like(x)
         conv_fwd_raw(dy, wt1, None, dx, N, H, W, Cout, Cin, ks)
     return dx
+
+
+def _placeholder(shape, dtype, device):
+    """A tensor of this shape that no kernel may read or write: one element, expanded."""
+    return torch.empty(1, dtype=dtype, device=device).expand(shape)
+
+
+def _pro3(x, ipro, ks):
+    """(x, ipro) for a conv's forward and weight gradient.  A 3x3 conv gathers each input
+    element for 9 taps, so its load prologue would apply the input BatchNorm 9 times per
+    element: on large maps act(BN(x)) is written once instead (the same rounded values) and
+    the prologue dropped (the heads' 128 -> 128 convs, catch_net.py:301-304)."""
+    if ks == 3 and ipro is not None and x.numel() // x.shape[-1] >= 16384 and "pro3" not in _DISABLE:
+        return _bn_apply_raw(x, ipro, None, torch.empty_like(x)), None
+    return x, ipro
 
 
 class _ConvBN(torch.autograd.Function):
@@ -991,51 +1019,33 @@ class _ConvBN(torch.autograd.Function):
         Cout = w.shape[0]
         assert w.shape == (Cout, ks, ks, Cin), (tuple(w.shape), ks, Cin)
         wt = _prep(w, 0, x.dtype, Cout, Cin, ks)
-        ctx.nostore = training and ks == 1 and b is None and act == ROD_ACT_RELU6 and \
-            _nostore_ok(x, ipro, N, H, W, Cin, Cout, dw_stride)
-        if not training and ks == 1 and b is None and act == ROD_ACT_RELU6 and \
-                _nostore_eval_ok(x, N, H, W, Cin, Cout, dw_stride):
-            # inference: nothing is computed here; the depthwise forms the values from x
-            y = torch.empty(1, dtype=x.dtype, device=x.device).expand(N, H, W, Cout)
+        expand = ks == 1 and b is None and act == ROD_ACT_RELU6   # the shape of a block's expand conv
+        ctx.nostore = training and expand and _nostore_ok(x, ipro, N, H, W, Cin, Cout, dw_stride)
+        nostore_eval = not training and expand and _nostore_eval_ok(x, N, H, W, Cin, Cout, dw_stride)
+        if ctx.nostore or nostore_eval:
+            # the expanded tensor is never written (ABI 23): a placeholder of its shape that no
+            # kernel reads (its consumers recompute it from x)
+            y = _placeholder((N, H, W, Cout), x.dtype, x.device)
             y._rod_expand = (x, ipro, wt, Cin)
             y._rod_nostore = True
+        if nostore_eval:
+            # inference: nothing is computed here; the depthwise forms the values from x
             mean, rstd = bn_statistics(y, mm, mv, False, decay, eps)
             ctx.training = False
             ctx.mark_non_differentiable(mean, rstd)
             return y, mean, rstd
-        if ctx.nostore:
-            # the expanded tensor is never written (ABI 23): a placeholder of its shape that no
-            # kernel reads (its consumers recompute it from x), the statistics from x alone
-            y = torch.empty(1, dtype=x.dtype, device=x.device).expand(N, H, W, Cout)
-            parts = torch.empty((-(-(N * H * W) // 128), 3, Cout), dtype=torch.float32, device=x.device)
+        parts = _conv_stat_parts(N * H * W, Cout, x.device) if training else None
+        if ctx.nostore:   # the statistics from x alone
             _abi.call("rod_conv_fwd_stats", x, *_pro_args(ipro), wt, parts, N * H * W, Cin, Cout, dtcode(x), stream())
-            y._rod_expand = (x, ipro, wt, Cin)
-            y._rod_nostore = True
-            mean, rstd = bn_statistics(y, mm, mv, training, decay, eps, parts)
             ctx.src_dw = None
-            ctx.save_for_backward(x, w, b, y, mean, rstd)
-            ctx.ks, ctx.ipro, ctx.gb, ctx.act, ctx.training = ks, ipro, (gamma, beta), act, training
-            ctx.mark_non_differentiable(mean, rstd)
-            ctx.set_materialize_grads(False)
-            return y, mean, rstd
-        y = torch.empty((N, H, W, Cout), dtype=x.dtype, device=x.device)
-        parts = None
-        if training:
-            parts = torch.empty((-(-(N * H * W) // 128), 3, Cout), dtype=torch.float32, device=x.device)
-        if ks == 3 and ipro is not None and N * H * W >= 16384 and "pro3" not in _DISABLE:
-            # a 3x3 conv gathers each input element for 9 taps, so its load prologue would apply
-            # the input BatchNorm 9 times per element: write act(BN(x)) once instead (the same
-            # rounded values) and use it for the forward and the weight gradient
-            # (the heads' 128 -> 128 convs, catch_net.py:301-304)
-            xb = torch.empty_like(x)
-            im, ir, ig, ib, ia = ipro
-            _abi.call("rod_bn_apply", x, im, ir, ig, ib, None, xb, N * H * W, Cin, 0, 0, 0, ia, dtcode(x), stream())
-            x, ipro = xb, None
-        ctx.src_dw = getattr(x, "_rod_dw", None)   # x is a depthwise output (_DWBN.forward)
-        conv_fwd_raw(x, wt, b, y, N, H, W, Cin, Cout, ks, parts, ipro)
-        if ks == 1 and b is None and training and x.dtype == torch.bfloat16 and Cin <= 32:
-            # an expand conv: the consumer depthwise may recompute y from x (dw_rc_ok, ABI 23)
-            y._rod_expand = (x, ipro, wt, Cin)
+        else:
+            y = torch.empty((N, H, W, Cout), dtype=x.dtype, device=x.device)
+            x, ipro = _pro3(x, ipro, ks)
+            ctx.src_dw = getattr(x, "_rod_dw", None)   # x is a depthwise output (_DWBN.forward)
+            conv_fwd_raw(x, wt, b, y, N, H, W, Cin, Cout, ks, parts, ipro)
+            if ks == 1 and b is None and training and x.dtype == torch.bfloat16 and Cin <= 32:
+                # an expand conv: the consumer depthwise may recompute y from x (dw_rc_ok, ABI 23)
+                y._rod_expand = (x, ipro, wt, Cin)
         mean, rstd = bn_statistics(y, mm, mv, training, decay, eps, parts)
         ctx.save_for_backward(x, w, b, y, mean, rstd)
         ctx.ks, ctx.ipro, ctx.gb, ctx.act, ctx.training = ks, ipro, (gamma, beta), act, training
@@ -1045,8 +1055,10 @@ class _ConvBN(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dz, *_):
+        def ret(dx=None):   # only x takes a gradient from autograd: the parameters' go to their slots
+            return dx, None, None, None, None, None, None
         if dz is None:
-            return None, None, None, None, None, None, None
+            return ret()
         if not ctx.training:
             raise RuntimeError("BatchNorm backward in inference mode is not part of the reference graph")
         x, w, b, y, mean, rstd = ctx.saved_tensors
@@ -1079,17 +1091,17 @@ class _ConvBN(torch.autograd.Function):
                 dyp, xparts = pw_bwd_gred(dz, y, mean, rstd, gamma, beta, ctx.act, coef, x, ctx.ipro, wt1,
                                           grad_slot(w), dyp=True)
                 _mark_written(w)
-                dx = torch.empty(1, dtype=x.dtype, device=x.device).expand(x.shape)
-                _put_dz_recipe(dx, (dyp, wt1, Cout))
+                dx = _placeholder(x.shape, x.dtype, x.device)
+                _DZ_RECIPE.put(dx, (dyp, wt1, Cout))
                 _put_bn_parts(dx, xparts)
-                return dx, None, None, None, None, None, None
+                return ret(dx)
             # the 16 -> 96 expand: its pre-BatchNorm y recomputed from x in the kernel (ABI 23)
             wt0 = _prep(w, 0, x.dtype, Cout, Cin, 1) if ctx.nostore or pw_bwd_rc_ok(M, Cin, Cout, x.dtype) else None
             dx, xparts = pw_bwd_gred(dz, y, mean, rstd, gamma, beta, ctx.act, coef, x, ctx.ipro, wt1, grad_slot(w),
                                      wt0=wt0)
             _mark_written(w)
             _put_bn_parts(dx, xparts)
-            return dx, None, None, None, None, None, None
+            return ret(dx)
         if ctx.nostore and not (ctx.ks == 1 and _pw_fused_ok(M, Cin, Cout, y.dtype) and (need_dx or _needs(w))):
             raise RuntimeError("expand conv without a stored output reached a backward path that reads it")
         if ctx.ks == 3 and not need_dx and b is None and ctx.ipro is None and _needs(w) and \
@@ -1101,7 +1113,7 @@ class _ConvBN(torch.autograd.Function):
             _abi.call("rod_stem_wgrad_bn", x, dz, y, mean, rstd, gamma, beta, ctx.act, coef, grad_slot(w), ws, N, H,
                       W, Cin, Cout, 3, dtcode(y), stream())
             _mark_written(w)
-            return None, None, None, None, None, None, None
+            return ret()
         if ctx.ks == 1 and _pw_fused_ok(M, Cin, Cout, y.dtype) and (need_dx or _needs(w) or _needs(b)):
             coef = _bn_bwd_coef(parts, dz, y, mean, rstd, gamma, beta, ctx.act)
             gw = grad_slot(w) if _needs(w) else torch.empty((Cout, Cin), dtype=torch.float32, device=y.device)
@@ -1124,13 +1136,9 @@ class _ConvBN(torch.autograd.Function):
             dy, dx = conv_bwd_data_bn(dz, y, mean, rstd, gamma, beta, ctx.act, coef, w)
             _conv_bwd_from_dy(x, w, b, ctx.ks, dy, ctx.ipro, False)
         else:
-            if parts is not None:
-                coef = bn_bwd_coef_from_parts(parts, M, Cout, rstd, gamma, beta, _needs(gamma), _needs(beta))
-                dy = _bn_bwd_apply(dz, y, mean, rstd, gamma, beta, ctx.act, coef)
-            else:
-                dy = bn_bwd_dy(dz, y, mean, rstd, gamma, beta, ctx.act, _needs(gamma), _needs(beta))
+            dy = _bn_bwd_dy_owned(parts, dz, y, mean, rstd, gamma, beta, ctx.act)
             dx = _conv_bwd_from_dy(x, w, b, ctx.ks, dy, ctx.ipro, need_dx)
-        return dx, None, None, None, None, None, None
+        return ret(dx)
 
 
 class _DWBN(torch.autograd.Function):
@@ -1172,8 +1180,10 @@ class _DWBN(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dz, *_):
+        def ret(dx=None):
+            return dx, None, None, None, None
         if dz is None:
-            return None, None, None, None, None
+            return ret()
         if not ctx.training:
             raise RuntimeError("BatchNorm backward in inference mode is not part of the reference graph")
         x, w, y, mean, rstd = ctx.saved_tensors
@@ -1182,7 +1192,7 @@ class _DWBN(torch.autograd.Function):
         # the BatchNorm-backward sums of (dz, y) when the project conv's fused backward formed
         # them (rod_pw_bwd_gred / rod_pw_bwd_gred_dyp in _ConvBN.backward)
         parts = _take_bn_parts(dz)
-        recipe = _take_dz_recipe(dz)   # dz unmaterialised: dy_p, W_p^T of the project (ABI 20)
+        recipe = _DZ_RECIPE.take(dz, strict=True)   # dz unmaterialised: dy_p, W_p^T of the project (ABI 20)
         fusable = _needs(w) and ctx.needs_input_grad[0] and _dw_fused_ok(N, Ho, Wo, C, x.dtype, s)
 
         def fused(entry, head, coef, geo):
@@ -1199,16 +1209,13 @@ class _DWBN(torch.autograd.Function):
             _mark_written(w)
             if gparts is not None:
                 _put_bn_parts(dx, gparts)
-            return dx, None, None, None, None
+            return ret(dx)
         if recipe is not None and parts is not None and fusable and s == 1 and ctx.ipro is not None:
             # dz recomputed per tile from dy_p (rod_dw3x3_bwd_fused_pw; stride 1: pt = pl = 1)
             coef = _bn_bwd_coef(parts, None, y, mean, rstd, gamma, beta, ctx.act)
             return fused("rod_dw3x3_bwd_fused_pw", (x, *_pro_args(ctx.ipro), *recipe), coef, ())
         if recipe is not None:   # any other path: the dz the project would have written
             dz = _materialize_dz(recipe, (N, Ho, Wo, C), y.dtype)
-            if parts is not None:
-                _put_bn_parts(dz, parts)
-                parts = _take_bn_parts(dz)
         if ctx.rc_src is not None:
             # the input (the expand's output) was never written: the stride-2 fused backward
             # recomputes it from the block input (ABI 23)
@@ -1225,22 +1232,10 @@ class _DWBN(torch.autograd.Function):
             dz = dz.contiguous()
             coef = _bn_bwd_coef(parts, dz, y, mean, rstd, gamma, beta, ctx.act)
             return fused("rod_dw3x3_bwd_fused", (x, *_pro_args(ctx.ipro), dz), coef, (s, pt, pl, Ho, Wo))
-        if parts is not None:
-            coef = _bn_bwd_coef(parts, dz, y, mean, rstd, gamma, beta, ctx.act)
-            dy = _bn_bwd_apply(dz, y, mean, rstd, gamma, beta, ctx.act, coef)
-        else:
-            dy = bn_bwd_dy(dz, y, mean, rstd, gamma, beta, ctx.act, _needs(gamma), _needs(beta))
+        dy = _bn_bwd_dy_owned(parts, dz, y, mean, rstd, gamma, beta, ctx.act)
         if _needs(w):
-            ws = workspace(_abi.query("rod_dw3x3_bwd_filter_workspace", N, Ho, Wo, C), x.device)
-            _abi.call("rod_dw3x3_bwd_filter", x, *_pro_args(ctx.ipro), dy, grad_slot(w), ws, N, H, W, C, s, pt, pl,
-                      Ho, Wo, dtcode(x), stream())
-            _mark_written(w)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            _abi.call("rod_dw3x3_bwd_data", dy, w, dx, *_gred_args(None), N, H, W, C, s, pt, pl, Ho, Wo, dtcode(x),
-                      stream())
-        return dx, None, None, None, None
+            _dw_bwd_filter(x, ctx.ipro, dy, w, ctx.geo)
+        return ret(_dw_bwd_data(dy, w, x, ctx.geo) if ctx.needs_input_grad[0] else None)
 
 
 def _dw_fused_ok(N, Ho, Wo, C, dtype, stride=1):
@@ -1314,21 +1309,12 @@ def conv2d_bn_act(x, w, b, ksize, gamma, beta, mmean, mvar, act, training, decay
         # so the implicit GEMM's rows are 16-byte aligned (1080p b8 99 -> 99 at 34x60: 124 us
         # unpadded, 31 us for 128 -> 128 on the same map, tools/conv_bench.py).  The padded k
         # columns add exact zeros; the k-chunking of the sum differs (a rounding-level change).
-        xb = torch.zeros((N, H, W, cp), dtype=xt.dtype, device=xt.device)
-        im, ir, ig, ib, ia = ipro
-        _abi.call("rod_bn_apply", xt, im, ir, ig, ib, None, xb, N * H * W, Cin, 0, 0, cp, ia, dtcode(xt), stream())
-        xt, ipro = xb, None
+        xt = _bn_apply_raw(xt, ipro, None, torch.zeros((N, H, W, cp), dtype=xt.dtype, device=xt.device), ldo=cp)
+        ipro = None
         wt = _cinpad_weights(w, cp, xt.dtype)
         Cin = cp
-    elif ksize == 3 and ipro is not None and N * H * W >= 16384 and "pro3" not in _DISABLE:
-        # as _ConvBN.forward: a 3x3 gathers every input element 9 times, so act(BN(x)) is written
-        # once instead of applied in the load prologue (the same rounded values)
-        xb = torch.empty_like(xt)
-        im, ir, ig, ib, ia = ipro
-        _abi.call("rod_bn_apply", xt, im, ir, ig, ib, None, xb, N * H * W, Cin, 0, 0, 0, ia, dtcode(xt), stream())
-        xt, ipro = xb, None
-        wt = _prep(w, 0, xt.dtype, Cout, Cin, ksize)
     else:
+        xt, ipro = _pro3(xt, ipro, ksize)   # as _ConvBN.forward
         wt = _prep(w, 0, xt.dtype, Cout, Cin, ksize)
     z = torch.empty((N, H, W, Cout), dtype=xt.dtype, device=xt.device)
     mean, rstd = bn_statistics(z, mmean, mvar, False, decay, eps)
@@ -1352,12 +1338,8 @@ class _BNApplyOwned(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, residual, mean, rstd, gamma, beta, act):
-        N, H, W, C = y.shape
-        out = torch.empty_like(y)
-        _abi.call("rod_bn_apply", y, mean, rstd, gamma, beta, residual, out, N * H * W, C, 0, 0, 0, act, dtcode(y),
-                  stream())
         ctx.has_res = residual is not None
-        return out
+        return _bn_apply_raw(y, (mean, rstd, gamma, beta, act), residual, torch.empty_like(y))
 
     @staticmethod
     def backward(ctx, g):
@@ -1617,11 +1599,7 @@ class _Deconv2x2(torch.autograd.Function):
             wt1 = _prep(w, 1, dy.dtype, 4 * F, Cin, 1)
             dx = torch.empty_like(x)
             conv_fwd_raw(dz, wt1, None, dx, N, h, wd, 4 * F, Cin, 1)
-        if ctx.needs_input_grad[1]:
-            ws = workspace(_abi.query("rod_conv_wgrad_workspace", N, h, wd, Cin, 4 * F, 1), x.device)
-            _abi.call("rod_conv_wgrad", x, *_pro_args(None), dz, grad_slot(w), None, ws, N, h, wd, Cin, 4 * F, 1,
-                      0, 0, dtcode(x), stream())
-            _mark_written(w)
+        _conv_wgrad(x, None, dz, w, None, ctx.needs_input_grad[1], False, (N, h, wd, Cin, 4 * F, 1))
         return dx, None, None, None
 
 
@@ -1761,16 +1739,13 @@ def softmax(logits, K):
 
 
 class _SoftmaxCEHNM(torch.autograd.Function):
+    """Hard-negative-mining cross-entropy.  produce(want_grad) -> (out [8], grad or None) runs
+    the kernels: the single launch (softmax_ce_hnm) or one data-parallel shard of hnm_lockstep
+    (softmax_ce_hnm_dp)."""
+
     @staticmethod
-    def forward(ctx, logits, det_lbl, det_pos, iou, lvl_off, bs):
-        B, A, K = logits.shape
-        L = len(lvl_off) - 1
-        out = torch.empty(8, dtype=torch.float32, device=logits.device)
-        grad = torch.empty_like(logits) if ctx.needs_input_grad[0] else None
-        ws = workspace(_abi.query("rod_softmax_ce_hnm_workspace", B, A, L), logits.device)
-        _abi.call("rod_softmax_ce_hnm", logits.contiguous(), det_lbl, det_pos, iou,
-                  np.ascontiguousarray(lvl_off, dtype=np.int32), L, float(bs), out, grad, ws, B, A, K,
-                  dtcode(logits), stream())
+    def forward(ctx, logits, det_lbl, det_pos, iou, lvl_off, bs, produce):
+        out, grad = produce(ctx.needs_input_grad[0])
         ctx.save_for_backward(grad, logits, det_lbl, det_pos, iou)
         ctx.hnm = (lvl_off, bs)
         ctx.set_materialize_grads(False)
@@ -1781,17 +1756,27 @@ class _SoftmaxCEHNM(torch.autograd.Function):
     def backward(ctx, g_vec, g_loss):
         grad, logits, det_lbl, det_pos, iou = ctx.saved_tensors
         if g_loss is None:
-            return None, None, None, None, None, None
+            return None, None, None, None, None, None, None
         # clf_loss enters the training loss with weight 1 (net_tools.det_clf_loss); the IoU
         # factor passes gradient to iou when refine_out is trained (fix_refine=False)
         g_iou = _iou_factor_grad(logits, det_lbl, det_pos, iou, *ctx.hnm) if ctx.needs_input_grad[3] else None
-        return grad, None, None, g_iou, None, None
+        return grad, None, None, g_iou, None, None, None
 
 
 def softmax_ce_hnm(logits, det_lbl, det_pos, iou, lvl_off, bs):
     """([8] pos_loss, neg_loss, clf_loss, max_hard_pred, n_pos, k, n_neg_selected, 0;
     clf_loss as a differentiable 0-d view)."""
-    return _SoftmaxCEHNM.apply(logits, det_lbl, det_pos, iou, lvl_off, bs)
+    def produce(want_grad):
+        B, A, K = logits.shape
+        L = len(lvl_off) - 1
+        out = torch.empty(8, dtype=torch.float32, device=logits.device)
+        grad = torch.empty_like(logits) if want_grad else None
+        ws = workspace(_abi.query("rod_softmax_ce_hnm_workspace", B, A, L), logits.device)
+        _abi.call("rod_softmax_ce_hnm", logits.contiguous(), det_lbl, det_pos, iou,
+                  np.ascontiguousarray(lvl_off, dtype=np.int32), L, float(bs), out, grad, ws, B, A, K,
+                  dtcode(logits), stream())
+        return out, grad
+    return _SoftmaxCEHNM.apply(logits, det_lbl, det_pos, iou, lvl_off, bs, produce)
 
 
 def hnm_lockstep(shards, lvl_off, bs, B_global, allreduce, want_grad=True):
@@ -1834,32 +1819,13 @@ def hnm_lockstep(shards, lvl_off, bs, B_global, allreduce, want_grad=True):
     return res
 
 
-class _SoftmaxCEHNMDP(torch.autograd.Function):
-    """softmax_ce_hnm for one data-parallel shard (hnm_lockstep with the process group)."""
-
-    @staticmethod
-    def forward(ctx, logits, det_lbl, det_pos, iou, lvl_off, bs, B_global, allreduce):
-        ((out, grad),) = hnm_lockstep([(logits, det_lbl, det_pos, iou)], lvl_off, bs, B_global, allreduce,
-                                      want_grad=ctx.needs_input_grad[0])
-        ctx.save_for_backward(grad, logits, det_lbl, det_pos, iou)
-        ctx.hnm = (lvl_off, bs)
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(out)
-        return out, out[2]
-
-    @staticmethod
-    def backward(ctx, g_vec, g_loss):
-        grad, logits, det_lbl, det_pos, iou = ctx.saved_tensors
-        if g_loss is None:
-            return None, None, None, None, None, None, None, None
-        g_iou = _iou_factor_grad(logits, det_lbl, det_pos, iou, *ctx.hnm) if ctx.needs_input_grad[3] else None
-        return grad, None, None, g_iou, None, None, None, None
-
-
 def softmax_ce_hnm_dp(logits, det_lbl, det_pos, iou, lvl_off, bs, B_global, allreduce):
     """softmax_ce_hnm with the hard negatives selected over the GLOBAL batch of a data-parallel
     job (allreduce: in-place SUM of a list of device int32 tensors over the ranks)."""
-    return _SoftmaxCEHNMDP.apply(logits, det_lbl, det_pos, iou, lvl_off, bs, B_global, allreduce)
+    def produce(want_grad):
+        return hnm_lockstep([(logits, det_lbl, det_pos, iou)], lvl_off, bs, B_global, allreduce,
+                            want_grad=want_grad)[0]
+    return _SoftmaxCEHNM.apply(logits, det_lbl, det_pos, iou, lvl_off, bs, produce)
 
 
 def _softmax_focal_raw(logits, det_lbl, det_pos, alpha, gamma, want_grad):
@@ -1873,9 +1839,11 @@ def _softmax_focal_raw(logits, det_lbl, det_pos, alpha, gamma, want_grad):
 
 
 class _SoftmaxFocal(torch.autograd.Function):
+    """Focal loss; produce(want_grad) -> (out [8], grad or None) as for _SoftmaxCEHNM."""
+
     @staticmethod
-    def forward(ctx, logits, det_lbl, det_pos, alpha, gamma):
-        out, grad = _softmax_focal_raw(logits, det_lbl, det_pos, alpha, gamma, ctx.needs_input_grad[0])
+    def forward(ctx, logits, produce):
+        out, grad = produce(ctx.needs_input_grad[0])
         ctx.save_for_backward(grad)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(out)
@@ -1885,18 +1853,23 @@ class _SoftmaxFocal(torch.autograd.Function):
     def backward(ctx, g_vec, g_loss):
         (grad,) = ctx.saved_tensors
         # clf_loss enters the training loss with weight 1 (net_tools.det_clf_loss)
-        return (grad if g_loss is not None else None), None, None, None, None
+        return (grad if g_loss is not None else None), None
+
+
+def _focal(logits, produce):
+    """The gradient is written by the forward launch, and only when it can be asked for: logits
+    requires grad and grad mode is on."""
+    if not (torch.is_grad_enabled() and logits.requires_grad):
+        out, _ = produce(False)
+        return out, out[2]
+    return _SoftmaxFocal.apply(logits, produce)
 
 
 def softmax_focal(logits, det_lbl, det_pos, alpha, gamma):
     """Focal loss of the ODM classifier (rod_softmax_focal; opt-in, replaces hard-negative mining
     AND the IoU factor): ([8] pos_loss, neg_loss, clf_loss, 0, n_pos, 0, n_neg, norm; clf_loss as
-    a differentiable 0-d view).  The gradient is written by the forward launch, and only when it
-    can be asked for: logits requires grad and grad mode is on."""
-    if not (torch.is_grad_enabled() and logits.requires_grad):
-        out, _ = _softmax_focal_raw(logits, det_lbl, det_pos, alpha, gamma, False)
-        return out, out[2]
-    return _SoftmaxFocal.apply(logits, det_lbl, det_pos, alpha, gamma)
+    a differentiable 0-d view)."""
+    return _focal(logits, lambda want_grad: _softmax_focal_raw(logits, det_lbl, det_pos, alpha, gamma, want_grad))
 
 
 def focal_lockstep(shards, alpha, gamma, allreduce, want_grad=True):
@@ -1925,31 +1898,11 @@ def focal_lockstep(shards, alpha, gamma, allreduce, want_grad=True):
     return res
 
 
-class _SoftmaxFocalDP(torch.autograd.Function):
-    """softmax_focal for one data-parallel shard (focal_lockstep with the process group)."""
-
-    @staticmethod
-    def forward(ctx, logits, det_lbl, det_pos, alpha, gamma, allreduce):
-        ((out, grad),) = focal_lockstep([(logits, det_lbl, det_pos)], alpha, gamma, allreduce,
-                                        want_grad=ctx.needs_input_grad[0])
-        ctx.save_for_backward(grad)
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(out)
-        return out, out[2]
-
-    @staticmethod
-    def backward(ctx, g_vec, g_loss):
-        (grad,) = ctx.saved_tensors
-        return (grad if g_loss is not None else None), None, None, None, None, None
-
-
 def softmax_focal_dp(logits, det_lbl, det_pos, alpha, gamma, allreduce):
     """softmax_focal normalised by the positives of the GLOBAL batch of a data-parallel job
     (allreduce: in-place SUM of a list of device int32 tensors over the ranks)."""
-    if not (torch.is_grad_enabled() and logits.requires_grad):
-        ((out, _),) = focal_lockstep([(logits, det_lbl, det_pos)], alpha, gamma, allreduce, want_grad=False)
-        return out, out[2]
-    return _SoftmaxFocalDP.apply(logits, det_lbl, det_pos, alpha, gamma, allreduce)
+    return _focal(logits, lambda want_grad: focal_lockstep([(logits, det_lbl, det_pos)], alpha, gamma, allreduce,
+                                                           want_grad=want_grad)[0])
 
 
 def select_topk_nms(probs, boxes, select_threshold, top_k, keep_top_k, nms_threshold, compact=True):
@@ -2062,17 +2015,7 @@ class _ConvAct(torch.autograd.Function):
             conv_fwd_raw(dy, _prep_flat(w, 1, x.dtype), None, dcol, N, Ho, Wo, Cout, 9 * Cin, 1)
             dx = torch.empty_like(x)
             _abi.call("rod_col2im3x3", dcol, dx, N, H, W, Cin, s, pt, pl, Ho, Wo, dtcode(x), stream())
-        need_w, need_bias = _needs(w), _needs(b)
-        if need_w or need_bias:
-            gw = grad_slot(w) if need_w else torch.empty(w.shape, dtype=torch.float32, device=x.device)
-            gb = grad_slot(b) if need_bias else None
-            ws = workspace(_abi.query("rod_conv_wgrad_workspace", N, Ho, Wo, 9 * Cin, Cout, 1), x.device)
-            _abi.call("rod_conv_wgrad", col, *_pro_args(None), dy, gw, gb, ws, N, Ho, Wo, 9 * Cin, Cout, 1, 0, 0,
-                      dtcode(x), stream())
-            if need_w:
-                _mark_written(w)
-            if need_bias:
-                _mark_written(b)
+        _conv_wgrad(col, None, dy, w, b, _needs(w), _needs(b), (N, Ho, Wo, 9 * Cin, Cout, 1))
         return dx, None, None, None, None, None, None
 
 

@@ -138,6 +138,37 @@ def test_bn_parts_handoff_rejects_summed_gradient():
     ops.clear_bn_parts()
 
 
+def test_dz_recipe_handoff_raises_on_modified_or_aliased_placeholder():
+    """The gradient-recipe hand-off from the project conv's backward to its depthwise
+    (ops._DZ_RECIPE) follows the same identity rule, taken strictly: the recipe comes back for
+    the very placeholder or a same-storage view of it, a placeholder summed into in place or a
+    tensor of another shape at the same address raises, and clear_bn_parts counts the recipes
+    nobody took and empties both registries."""
+    dz = torch.zeros(4, 8)
+    recipe = (torch.ones(4, 2), torch.ones(2, 8), 2)
+    ops._DZ_RECIPE.put(dz, recipe)
+    assert ops._DZ_RECIPE.take(dz, strict=True) is recipe
+    assert ops._DZ_RECIPE.take(dz, strict=True) is None      # taken once
+    ops._DZ_RECIPE.put(dz, recipe)
+    assert ops._DZ_RECIPE.take(dz.view(4, 8), strict=True) is recipe
+    ops._DZ_RECIPE.put(dz, recipe)
+    dz.add_(torch.ones(4, 8))
+    with pytest.raises(RuntimeError, match="modified or aliased"):
+        ops._DZ_RECIPE.take(dz, strict=True)
+    assert ops.clear_bn_parts() == 0                           # a refused take pops its entry too
+    ops._DZ_RECIPE.put(dz, recipe)
+    alias = dz.view(8, 4)                                      # another tensor, the same data_ptr()
+    assert alias.data_ptr() == dz.data_ptr()
+    with pytest.raises(RuntimeError, match="modified or aliased"):
+        ops._DZ_RECIPE.take(alias, strict=True)
+    ops._DZ_RECIPE.put(dz, recipe)
+    ops._DZ_RECIPE.put(torch.zeros(2, 3), recipe)
+    ops._put_bn_parts(dz, torch.ones(2, 2, 8))
+    assert ops.clear_bn_parts() == 2
+    assert not ops._DZ_RECIPE.entries and not ops._BN_PARTS.entries
+    assert ops.clear_bn_parts() == 0
+
+
 def test_switches_reject_unknown_tokens():
     """ops._switches: the known tokens parse, an empty value is the empty set, and a token the
     code does not read — a retired path (gred, side) or a misspelling — raises, naming it."""
