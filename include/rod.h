@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ROD_ABI_VERSION 26
+#define ROD_ABI_VERSION 27
 #define ROD_EINVAL (-1)
 
 enum { ROD_F32 = 0, ROD_BF16 = 1, ROD_I32 = 2 /* collectives only (ABI 19) */ };
@@ -551,6 +551,42 @@ size_t rod_smoothl1_workspace(int B, int A);
 int rod_smoothl1_masked(const void* pred, const float* target, const int* mask,
                         const int* lvl_off, int L, float scale, float* loss_lvl, void* grad,
                         float* grad_target, void* workspace, int B, int A, int dtype, void* stream);
+/* IoU-family regression loss of the ODM box (ABI 27; opt-in, the reference has only the smooth-L1
+ * above): Rezatofighi et al. 2019 (GIoU), Zheng et al. 2020 (DIoU, CIoU).  The box the ODM predicts
+ * for anchor a is decode(anchor_a, refine_out_a + det_out_a), what rod_decode forms with off_b; the
+ * target is the matched centre box cbox_a (rod_match_anchors), the mask det_pos.  Per row with
+ * det_pos != 0, in fp32, one rounding per operation, exp and atan correctly rounded:
+ *   s = to_f32(refine_out) + to_f32(det_out)
+ *   cy = s0 ah + acy, cx = s1 aw + acx, h = exp(s2) ah, w = exp(s3) aw             (the prediction)
+ *   (py0, px0, py1, px1) = (cy - h/2, cx - w/2, cy + h/2, cx + w/2); (gy0, ..) likewise from cbox
+ *   I = max(min(py1, gy1) - max(py0, gy0), 0) max(min(px1, gx1) - max(px0, gx0), 0)
+ *   U = (px1 - px0)(py1 - py0) - I + (gy1 - gy0)(gx1 - gx0), IoU = I / U      (rod_det_targets' jaccard)
+ *   eh = max(py1, gy1) - min(py0, gy0), ew = max(px1, gx1) - min(px0, gx0)       (the enclosing box)
+ *   C = eh ew, c2 = eh eh + ew ew, rho2 = (cy - gcy)^2 + (cx - gcx)^2
+ *   v = (4 / pi^2) (atan(gw / gh) - atan(w / h))^2, alpha = v / ((1 - IoU) + v), 0 when v == 0
+ *   kind 0 IoU:  1 - IoU            kind 1 GIoU: 1 - IoU + (C - U) / C
+ *   kind 2 DIoU: 1 - IoU + rho2/c2  kind 3 CIoU: the DIoU loss + alpha v
+ * No epsilon: h, w > 0 make U, C, c2 > 0 for finite inputs; non-finite inputs give a non-finite loss.
+ * loss_lvl[l] = weight * (sum over the level's rows) / scale, loss_lvl[L] their sum in level order
+ * (fp32, device, L+1 entries); block sums go through a slab and a fixed-order fp64 finalize, no
+ * float atomics: run-to-run identical.
+ * grad (nullable, [B,A,4] in dtype) = d loss_lvl[L] / d s in closed form, written in the same pass:
+ * d/ds0 = ah d/dcy, d/ds1 = aw d/dcx, d/ds2 = h d/dh, d/ds3 = w d/dw through corners -> centre form ->
+ * decode; alpha is a constant (as in the CIoU paper); at ties max passes to the prediction when
+ * p >= g, min when p <= g, max(., 0) at >= 0 (the rule of rod_det_targets_bwd); times weight / scale.
+ * It is the gradient wrt det_out AND wrt refine_out (the prediction depends on their sum).  Rows
+ * with det_pos == 0 read det_pos alone, add 0 and get a zero gradient.
+ * anc_center fp32 [A,4]; refine_out / det_out [B,A,4] in dtype; cbox fp32 [B,A,4]; det_pos int [B,A];
+ * lvl_off host [L+1].  A row is one 16-byte (fp32) / 8-byte (bf16) load or store when every pointer
+ * is so aligned (the fp32 tables to 16), else the components go one by one: same results.
+ * kind outside 0..3, scale == 0, a weight that is negative or not finite, B or A <= 0, bad levels
+ * or a NULL required pointer: ROD_EINVAL before any HIP call, the message names the argument.
+ * Two kernels; no host synchronisation, no allocation.  workspace: rod_box_iou_loss_workspace(). */
+size_t rod_box_iou_loss_workspace(int B, int A);
+int rod_box_iou_loss(const float* anc_center, const void* refine_out, const void* det_out,
+                     const float* cbox, const int* det_pos, const int* lvl_off, int L, int kind,
+                     float weight, float scale, float* loss_lvl, void* grad, void* workspace, int B,
+                     int A, int dtype, void* stream);
 
 /* Box conversions on [n,4] fp32 (utils/common_tools.py:16-56):
  * to_center=1: (ymin,xmin,ymax,xmax) -> (cy,cx,h,w); 0: the inverse. */

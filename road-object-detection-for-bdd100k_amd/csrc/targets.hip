@@ -1,4 +1,5 @@
-// targets.hip — anchor matching (JACCARD_BIGGER) and the masked smooth-L1 loss.
+// targets.hip — anchor matching (JACCARD_BIGGER), the masked smooth-L1 loss and the opt-in
+// IoU-family box loss.
 //
 // Bit-exactness: this file is compiled with -ffp-contract=off (Makefile), so every
 // expression below rounds after each operation exactly like the reference's chain of
@@ -188,7 +189,8 @@ __global__ void __launch_bounds__(256) smoothl1_kernel(const T* __restrict__ pre
   if (threadIdx.x == 0) slab[(long)l * nbx + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
-__global__ void level_sum_finalize_kernel(const float* __restrict__ slab, int nbx, int L, float scale,
+// weight: 1 for the smooth-L1 losses (1 * x is x bit for bit), the loss weight of rod_box_iou_loss
+__global__ void level_sum_finalize_kernel(const float* __restrict__ slab, int nbx, int L, float weight, float scale,
                                           float* __restrict__ out) {
   // one 256-thread block: strided partial sums per level, fixed-order tree in LDS
   __shared__ double red[MAXL][256];
@@ -206,10 +208,153 @@ __global__ void level_sum_finalize_kernel(const float* __restrict__ slab, int nb
   if (threadIdx.x != 0) return;
   float total = 0.f;  // refine_loss = 0.; refine_loss += layer_loss (net_tools.py:505-515)
   for (int l = 0; l < L; ++l) {
-    out[l] = (float)red[l][0] / scale;  // reduce_sum(...) / bs
+    out[l] = weight * (float)red[l][0] / scale;  // reduce_sum(...) / bs
     total = total + out[l];
   }
   out[L] = total;
+}
+
+// ---------------------------------------------------------------- IoU-family box loss (ABI 27)
+// The four components of one row as ONE vector: 16 bytes (fp32) or 8 bytes (bf16); VEC = false
+// (a pointer off that alignment) loads and stores them one by one.
+template <typename T> struct Row4;
+template <> struct Row4<float> { typedef f32x4 V; };
+template <> struct Row4<bf16_t> { typedef bf16x4 V; };
+template <typename T, bool VEC>
+__device__ __forceinline__ void load_row4(const T* __restrict__ p, float (&o)[4]) {
+  if constexpr (VEC) {
+    const typename Row4<T>::V v = *(const typename Row4<T>::V*)p;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = (float)v[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = to_f32(p[k]);
+  }
+}
+template <typename T, bool VEC>
+__device__ __forceinline__ void store_row4(T* __restrict__ p, const float (&g)[4]) {
+  if constexpr (VEC) {
+    typename Row4<T>::V v;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = from_f32<T>(g[k]);
+    *(typename Row4<T>::V*)p = v;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) p[k] = from_f32<T>(g[k]);
+  }
+}
+__device__ __forceinline__ float atan_cr(float x) { return (float)atan((double)x); }
+
+// IoU / GIoU / DIoU / CIoU loss of the box the ODM predicts, decode(anchor, refine_out + det_out),
+// against the matched centre box, and its gradient wrt the summed offsets in the same pass (the
+// formula is in include/rod.h, rod_box_iou_loss).  Grid as smoothl1_kernel: x over (image,
+// anchor-in-level) pairs of one level, y = level.  A row off the mask loads det_pos alone.
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(256) box_iou_loss_kernel(const float* __restrict__ anc_center,
+                                                           const T* __restrict__ refine_out,
+                                                           const T* __restrict__ det_out,
+                                                           const float* __restrict__ cbox,
+                                                           const int* __restrict__ det_pos, LevelInfo li, int kind,
+                                                           float gscale, T* __restrict__ grad,
+                                                           float* __restrict__ slab, int B, int A, int nbx) {
+  __shared__ float red[4];
+  const int l = blockIdx.y;
+  const int Al = li.off[l + 1] - li.off[l];
+  const long total = (long)B * Al;
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  float rl = 0.f;
+  if (t < total) {
+    const int b = (int)(t / Al);
+    const int a = li.off[l] + (int)(t - (long)b * Al);
+    const long o = (long)b * A + a;
+    float g[4] = {0.f, 0.f, 0.f, 0.f};
+    if (det_pos[o] != 0) {
+      float az[4], gz[4], s[4], sb[4];
+      load_row4<float, VEC>(anc_center + (long)a * 4, az);
+      load_row4<float, VEC>(cbox + o * 4, gz);
+      load_row4<T, VEC>(refine_out + o * 4, s);
+      load_row4<T, VEC>(det_out + o * 4, sb);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) s[k] = s[k] + sb[k];  // refine_out + det_out, as rod_decode
+      const float cy = s[0] * az[2] + az[0], cx = s[1] * az[3] + az[1];
+      const float h = exp_cr(s[2]) * az[2], w = exp_cr(s[3]) * az[3];
+      const float py0 = cy - h / 2.f, px0 = cx - w / 2.f, py1 = cy + h / 2.f, px1 = cx + w / 2.f;
+      const float gy0 = gz[0] - gz[2] / 2.f, gx0 = gz[1] - gz[3] / 2.f;
+      const float gy1 = gz[0] + gz[2] / 2.f, gx1 = gz[1] + gz[3] / 2.f;
+      // jaccard with det_targets_kernel's operations
+      const float ph = py1 - py0, pw = px1 - px0;
+      const float ap = pw * ph;
+      const float ihr = fminf(py1, gy1) - fmaxf(py0, gy0);
+      const float iwr = fminf(px1, gx1) - fmaxf(px0, gx0);
+      const float ih = fmaxf(ihr, 0.f), iw = fmaxf(iwr, 0.f);
+      const float I = ih * iw;
+      const float U = ap - I + (gy1 - gy0) * (gx1 - gx0);
+      const float iou = I / U;
+      rl = 1.f - iou;
+      const float q = I / (U * U);
+      float d_I = -(1.f / U + q), d_ap = q;  // d(1 - iou) / d(I, area of the prediction)
+      float d_eh = 0.f, d_ew = 0.f, d_cy = 0.f, d_cx = 0.f, d_h = 0.f, d_w = 0.f;
+      if (kind != 0) {
+        // the enclosing box: height, width, area C, squared diagonal c2
+        const float eh = fmaxf(py1, gy1) - fminf(py0, gy0), ew = fmaxf(px1, gx1) - fminf(px0, gx0);
+        if (kind == 1) {
+          const float C = eh * ew;
+          rl = rl + (C - U) / C;
+          const float invC = 1.f / C, dC = U / (C * C);
+          d_I = d_I + invC;
+          d_ap = d_ap - invC;
+          d_eh = dC * ew;
+          d_ew = dC * eh;
+        } else {
+          const float c2 = eh * eh + ew * ew;
+          const float dy = cy - gz[0], dx = cx - gz[1];
+          const float rho2 = dy * dy + dx * dx;
+          rl = rl + rho2 / c2;
+          const float d_c2 = -(rho2 / (c2 * c2)), ir = 1.f / c2;
+          d_eh = d_c2 * (2.f * eh);
+          d_ew = d_c2 * (2.f * ew);
+          d_cy = ir * (2.f * dy);
+          d_cx = ir * (2.f * dx);
+          if (kind == 3) {
+            const float k4 = 0.40528473456935109f;  // 4 / pi^2
+            const float dat = atan_cr(gz[3] / gz[2]) - atan_cr(w / h);
+            const float v = k4 * (dat * dat);
+            const float alpha = v == 0.f ? 0.f : v / ((1.f - iou) + v);  // a constant in the gradient
+            rl = rl + alpha * v;
+            const float tv = alpha * ((2.f * k4) * dat), hw2 = h * h + w * w;
+            d_w = -(tv * (h / hw2));
+            d_h = tv * (w / hw2);
+          }
+        }
+      }
+      // max / min / max(., 0) with det_targets_bwd_kernel's rule, the prediction first
+      const float d_ih = ihr >= 0.f ? d_I * iw : 0.f;
+      const float d_iw = iwr >= 0.f ? d_I * ih : 0.f;
+      float d_py1 = py1 <= gy1 ? d_ih : 0.f, d_py0 = py0 >= gy0 ? -d_ih : 0.f;
+      float d_px1 = px1 <= gx1 ? d_iw : 0.f, d_px0 = px0 >= gx0 ? -d_iw : 0.f;
+      d_py1 += py1 >= gy1 ? d_eh : 0.f;
+      d_py0 += py0 <= gy0 ? -d_eh : 0.f;
+      d_px1 += px1 >= gx1 ? d_ew : 0.f;
+      d_px0 += px0 <= gx0 ? -d_ew : 0.f;
+      d_px1 += d_ap * ph;
+      d_px0 -= d_ap * ph;
+      d_py1 += d_ap * pw;
+      d_py0 -= d_ap * pw;
+      d_cy = d_cy + (d_py0 + d_py1);
+      d_cx = d_cx + (d_px0 + d_px1);
+      d_h = d_h + (d_py1 - d_py0) / 2.f;
+      d_w = d_w + (d_px1 - d_px0) / 2.f;
+      g[0] = d_cy * az[2] * gscale;
+      g[1] = d_cx * az[3] * gscale;
+      g[2] = d_h * h * gscale;
+      g[3] = d_w * w * gscale;
+    }
+    if (grad) store_row4<T, VEC>(grad + o * 4, g);
+  }
+  rl = warp_sum(rl);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = rl;
+  __syncthreads();
+  if (threadIdx.x == 0) slab[(long)l * nbx + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
 // ---------------------------------------------------------------- box conversions
@@ -320,9 +465,48 @@ int rod_smoothl1_masked(const void* pred, const float* target, const int* mask, 
     hipLaunchKernelGGL(smoothl1_kernel<T>, dim3(nbx, L), dim3(256), 0, s, (const T*)pred, target, mask, li, inv,
                        (T*)grad, grad_target, (float*)workspace, B, A, nbx);
   });
-  hipLaunchKernelGGL(level_sum_finalize_kernel, dim3(1), dim3(256), 0, s, (const float*)workspace, nbx, L, scale,
+  hipLaunchKernelGGL(level_sum_finalize_kernel, dim3(1), dim3(256), 0, s, (const float*)workspace, nbx, L, 1.f, scale,
                      loss_lvl);
   return check_launch("rod_smoothl1_masked");
+}
+
+size_t rod_box_iou_loss_workspace(int B, int A) { return rod_smoothl1_workspace(B, A); }
+
+int rod_box_iou_loss(const float* anc_center, const void* refine_out, const void* det_out, const float* cbox,
+                     const int* det_pos, const int* lvl_off, int L, int kind, float weight, float scale,
+                     float* loss_lvl, void* grad, void* workspace, int B, int A, int dtype, void* stream) {
+  ROD_CHECK_ARG(B > 0 && A > 0, "rod_box_iou_loss: B and A must be > 0, got B=%d A=%d", B, A);
+  ROD_CHECK_ARG(kind >= 0 && kind <= 3, "rod_box_iou_loss: kind must be 0 (IoU), 1 (GIoU), 2 (DIoU) or 3 (CIoU), got %d",
+                kind);
+  ROD_CHECK_ARG(scale != 0.f, "rod_box_iou_loss: scale must be non-zero");
+  ROD_CHECK_ARG(weight >= 0.f && weight <= 3.402823466e38f, "rod_box_iou_loss: weight must be finite and >= 0, got %g",
+                (double)weight);
+  ROD_CHECK_ARG(dtype == ROD_F32 || dtype == ROD_BF16, "rod_box_iou_loss: unsupported dtype code %d", dtype);
+  ROD_CHECK_ARG(lvl_off, "rod_box_iou_loss: lvl_off is a host array and must be given");
+  LevelInfo li;
+  int e = fill_levels(li, lvl_off, nullptr, L, A);
+  if (e) return e;
+  ROD_CHECK_ARG(anc_center && refine_out && det_out && cbox && det_pos,
+                "rod_box_iou_loss: anc_center/refine_out/det_out/cbox/det_pos NULL");
+  ROD_CHECK_ARG(workspace && loss_lvl, "rod_box_iou_loss: workspace/loss_lvl NULL");
+  const int nbx = smoothl1_nbx(B, li);
+  const float gscale = weight / scale;
+  hipStream_t s = ROD_STREAM(stream);
+  // one vector per row: 16 bytes (fp32 offsets) or 8 (bf16); the fp32 tables always 16
+  const uintptr_t am = dtype == ROD_F32 ? 15 : 7;
+  const bool vec = ((((uintptr_t)refine_out | (uintptr_t)det_out | (uintptr_t)grad) & am) |
+                    (((uintptr_t)anc_center | (uintptr_t)cbox) & 15)) == 0;
+  sel_dtype(dtype, [&](auto tt) {
+    typedef decltype(tt) T;
+    sel_bool(vec, [&](auto v) {
+      hipLaunchKernelGGL((box_iou_loss_kernel<T, decltype(v)::value>), dim3(nbx, L), dim3(256), 0, s, anc_center,
+                         (const T*)refine_out, (const T*)det_out, cbox, det_pos, li, kind, gscale, (T*)grad,
+                         (float*)workspace, B, A, nbx);
+    });
+  });
+  hipLaunchKernelGGL(level_sum_finalize_kernel, dim3(1), dim3(256), 0, s, (const float*)workspace, nbx, L, weight,
+                     scale, loss_lvl);
+  return check_launch("rod_box_iou_loss");
 }
 
 int rod_boxes_convert(const float* in, float* out, long n_boxes, int to_center, void* stream) {

@@ -1486,6 +1486,60 @@ def smooth_l1_masked(pred, target, mask, lvl_off, scale):
     return _SmoothL1.apply(pred, target, mask, lvl_off, scale)
 
 
+BOX_LOSS_KINDS = {'iou': 0, 'giou': 1, 'diou': 2, 'ciou': 3}
+
+
+def _box_iou_loss_raw(anc_center, refine_flat, det_flat, cbox, det_pos, lvl_off, kind, weight, scale, want_grad):
+    B, A, _ = det_flat.shape
+    L = len(lvl_off) - 1
+    if refine_flat.dtype != det_flat.dtype or refine_flat.shape != det_flat.shape:
+        raise ValueError("box_iou_loss: refine_flat and det_flat must agree in dtype and shape")
+    loss = torch.empty(L + 1, dtype=torch.float32, device=det_flat.device)
+    grad = torch.empty_like(det_flat, memory_format=torch.contiguous_format) if want_grad else None
+    ws = workspace(_abi.query("rod_box_iou_loss_workspace", B, A), det_flat.device)
+    _abi.call("rod_box_iou_loss", anc_center, refine_flat.contiguous(), det_flat.contiguous(), cbox, det_pos,
+              np.ascontiguousarray(lvl_off, dtype=np.int32), L, BOX_LOSS_KINDS.get(kind, kind), float(weight),
+              float(scale), loss, grad, ws, B, A, dtcode(det_flat), stream())
+    return loss, grad
+
+
+class _BoxIoULoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, refine_flat, det_flat, anc_center, cbox, det_pos, lvl_off, kind, weight, scale):
+        loss, grad = _box_iou_loss_raw(anc_center, refine_flat, det_flat, cbox, det_pos, lvl_off, kind, weight, scale,
+                                       ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        ctx.save_for_backward(grad)
+        ctx.wants = tuple(ctx.needs_input_grad[:2])
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(loss)
+        return loss, loss[len(lvl_off) - 1]
+
+    @staticmethod
+    def backward(ctx, g_vec, g_tot):
+        (grad,) = ctx.saved_tensors
+        if g_tot is None:
+            return (None,) * 9
+        # the seed-1 rule of _SmoothL1.backward; the prediction depends on refine_out + det_out, so
+        # the one buffer is the gradient of both
+        return (grad if ctx.wants[0] else None, grad if ctx.wants[1] else None) + (None,) * 7
+
+
+def box_iou_loss(anc_center, refine_flat, det_flat, cbox, det_pos, lvl_off, kind, weight, scale):
+    """IoU-family regression loss of the box the ODM predicts, decode(anchor, refine_flat + det_flat),
+    against the matched centre box over det_pos (rod_box_iou_loss; opt-in, in place of the masked
+    smooth-L1).  kind: 'iou' | 'giou' | 'diou' | 'ciou'.  Returns ([L+1] fp32 per-level
+    weight * sum / scale + total, total as a differentiable 0-d view).  The gradient is written by
+    the forward launch, only when it can be asked for; det_flat and (when it requires grad)
+    refine_flat receive the same tensor."""
+    if kind not in BOX_LOSS_KINDS:
+        raise ValueError("box_iou_loss: kind must be one of %s, got %r" % (sorted(BOX_LOSS_KINDS), kind))
+    if not (torch.is_grad_enabled() and (det_flat.requires_grad or refine_flat.requires_grad)):
+        loss, _ = _box_iou_loss_raw(anc_center, refine_flat, det_flat, cbox, det_pos, lvl_off, kind, weight, scale,
+                                    False)
+        return loss, loss[len(lvl_off) - 1]
+    return _BoxIoULoss.apply(refine_flat, det_flat, anc_center, cbox, det_pos, lvl_off, kind, weight, scale)
+
+
 # ----------------------------------------------------------------------------- targets
 def boxes_convert(boxes: torch.Tensor, to_center: bool) -> torch.Tensor:
     b = boxes.contiguous()

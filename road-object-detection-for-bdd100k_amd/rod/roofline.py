@@ -50,6 +50,14 @@ MI355X_BF16_PEAK_TFLOPS = 2500.0  # dense bf16 MFMA (spec, no sparsity)
 MI355X_F32_PEAK_TFLOPS = 157.3    # f32 MFMA / vector
 
 
+def box_iou_loss_bytes(B, A, es, n_pos, grad=True):
+    """Algorithmic bytes of rod_box_iou_loss: det_pos read and the gradient written for every row
+    (smooth-L1's bytes without det_gt and without the prediction off the mask), and for the n_pos
+    positive rows refine_out, det_out, cbox and the anchor.  cost() does not know n_pos and takes
+    every row as positive: an upper bound."""
+    return B * A * (4 + (4 * es if grad else 0)) + n_pos * (8 * es + 32)
+
+
 def cost(name, a):
     """(bytes, flops) of the call rod_<name>(*a)."""
     # ABI 3: rod_dw3x3_fwd / _bwd_filter / rod_conv_fwd / _wgrad carry the five BatchNorm
@@ -220,6 +228,9 @@ def cost(name, a):
         es = _ES[dt]
         wgt = a[8] is not None
         return B * A * (4 * es + 16 + 4 + 4 * es + (16 if wgt else 0)), 12 * B * A * 4
+    if name == "rod_box_iou_loss":
+        B, A, dt = a[13], a[14], a[15]
+        return box_iou_loss_bytes(B, A, _ES[dt], B * A, a[11] is not None), 80 * B * A
     if name == "rod_decode":
         B, A, dt = a[4], a[5], a[7]
         return B * A * (2 * 4 * _ES[dt] + 16) + 16 * A, 20 * B * A

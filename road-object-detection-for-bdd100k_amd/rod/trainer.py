@@ -13,6 +13,8 @@ bs, net_tools.py:513).  Clipping happens after the reduction (net_tools.py:649).
 BatchNorm statistics are per rank by default (documented deviation) or, with
 sync_bn=True, merged over the global batch (rod.ddp.SyncBatchNorm); the hard negatives are
 selected over the global batch (counts + radix histograms all-reduced, ops.hnm_lockstep).
+With loc_loss='iou' | 'giou' | 'diou' | 'ciou' (opt-in) the ODM box regression is that loss on the decoded
+boxes instead of the smooth-L1 on the offsets, normalised by the global batch like it (no collective).
 With clf_loss='focal' (opt-in) the classifier loss is the focal loss over every anchor instead,
 normalised by the positives of the global batch (one all-reduce of the counts, ops.focal_lockstep).
 """
@@ -37,7 +39,7 @@ class Trainer:
                  sync_bn=False, backbone_name='mobilenet_v2',
                  process_backbone_method=config.process_backbone_method.NONE, momentum=0.0, nesterov=False,
                  weight_decay=0.0, clip_norm=None, warmup_steps=0, fix_learning_rate=True, clf_loss='hnm',
-                 focal_alpha=0.25, focal_gamma=2.0):
+                 focal_alpha=0.25, focal_gamma=2.0, loc_loss='smooth_l1', loc_loss_weight=1.0):
         self.img_size = tuple(img_size)
         self.batch_size = batch_size          # per-rank batch
         self.world_size = world_size
@@ -79,6 +81,12 @@ class Trainer:
         if clf_loss not in ('hnm', 'focal'):
             raise ValueError("clf_loss must be 'hnm' or 'focal', got %r" % (clf_loss,))
         self.clf_loss, self.focal_alpha, self.focal_gamma = clf_loss, float(focal_alpha), float(focal_gamma)
+        # the ODM box regression loss: the reference's masked smooth-L1, or (opt-in) an IoU-family loss
+        if loc_loss != 'smooth_l1' and loc_loss not in ops.BOX_LOSS_KINDS:
+            raise ValueError("loc_loss must be 'smooth_l1', 'iou', 'giou', 'diou' or 'ciou', got %r" % (loc_loss,))
+        if not (0.0 <= float(loc_loss_weight) < float('inf')):
+            raise ValueError("loc_loss_weight must be finite and >= 0, got %r" % (loc_loss_weight,))
+        self.loc_loss, self.loc_loss_weight = loc_loss, float(loc_loss_weight)
         # BatchNorm over the global batch (opt-in; per-rank statistics otherwise)
         self.sync_bn = bool(sync_bn and (world_size > 1 or dp))
         if self.sync_bn:
@@ -217,18 +225,21 @@ class Trainer:
         else:
             refine_out, det_out, clf_out = out
             self.last_out = out
-            rflat = [None, None]
+            box = self.loc_loss != 'smooth_l1'
+            rflat = [None, None, None]
             if not self.fix_refine:
                 # refine_out feeds the refine loss AND the ODM targets / IoU factor (train.py:144-151,
                 # total_loss = refine + det + clf): one concatenation, two aliases whose gradients
-                # meet in rod_add
-                rflat = list(graph.fork(ops.levels_concat(refine_out, 4), 2))
+                # meet in rod_add; an IoU-family box loss decodes refine_out + det_out: a third
+                rflat = (list(graph.fork(ops.levels_concat(refine_out, 4), 3 if box else 2)) + [None])[:3]
             r_loss = net_tools.refine_loss(refine_out, tg[0], tg[3], targets=tg, scale=scale, refine_flat=rflat[0])
             dgt = net_tools.det_groundtruth(refine_out, tg[0], tg[1], tg[2], tg[3], self.anchors, targets=tg,
                                             refine_flat=rflat[1])
             d_loss, c_loss = net_tools.det_clf_loss(refine_out, clf_out, det_out, dgt, dgt[1], dgt[2], dgt[3],
                                                     scale=scale, clf_loss=self.clf_loss,
-                                                    focal_alpha=self.focal_alpha, focal_gamma=self.focal_gamma)
+                                                    focal_alpha=self.focal_alpha, focal_gamma=self.focal_gamma,
+                                                    loc_loss=self.loc_loss, loc_loss_weight=self.loc_loss_weight,
+                                                    refine_flat=rflat[2])
             loss = graph.scalar_sum(d_loss, c_loss) if self.fix_refine else graph.scalar_sum(r_loss, d_loss, c_loss)
             losses = (loss, r_loss, d_loss, c_loss)
             self.last_targets = (tg, dgt)

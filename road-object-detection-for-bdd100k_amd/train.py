@@ -18,6 +18,10 @@ only logs becomes the applied rate); any of them selects the momentum-SGD kernel
 
 Classifier loss (--train_range ALL): by default the reference's (hard-negative mining, IoU factor).
 --clf_loss focal replaces both by focal loss (--focal_alpha 0.25, --focal_gamma 2.0).
+
+Box regression loss of the ODM (--train_range ALL): by default the reference's (masked smooth-L1 on the
+encoded offsets).  --loc_loss iou|giou|diou|ciou replaces it by that loss between the decoded box and
+the matched box, times --loc_loss_weight (default 1.0).
 """
 import argparse
 import json
@@ -101,7 +105,24 @@ def parse(argv=None):
                     help='focal loss: weight of the positives, 1 - alpha on the negatives; in [0, 1] (default 0.25)')
     ap.add_argument('--focal_gamma', type=float, default=None,
                     help='focal loss: focusing exponent, finite and >= 0 (default 2.0)')
+    # box-regression addition (neutral by default: the reference's masked smooth-L1 on the offsets)
+    ap.add_argument('--loc_loss', default='smooth_l1', choices=['smooth_l1', 'iou', 'giou', 'diou', 'ciou'],
+                    help="ODM box regression loss (--train_range ALL): 'smooth_l1' = masked smooth-L1 on the encoded "
+                         "offsets (the reference); 'iou' / 'giou' / 'diou' / 'ciou' = that loss between the decoded "
+                         'box and the matched box, in its place')
+    ap.add_argument('--loc_loss_weight', type=float, default=None,
+                    help='weight of the IoU-family box loss in the training loss, finite and >= 0 (default 1.0)')
     F = ap.parse_args(argv)
+    loc_given = F.loc_loss_weight is not None
+    if F.loc_loss_weight is None:
+        F.loc_loss_weight = 1.0
+    if not (0.0 <= F.loc_loss_weight < float('inf')):      # (a NaN fails both comparisons)
+        ap.error('--loc_loss_weight must be finite and >= 0, got %r' % F.loc_loss_weight)
+    if F.train_range == 'REFINE' and (F.loc_loss != 'smooth_l1' or loc_given):
+        ap.error('--loc_loss / --loc_loss_weight need --train_range ALL: REFINE training has no ODM box loss to '
+                 'apply them to')
+    if F.loc_loss == 'smooth_l1' and loc_given:
+        ap.error('--loc_loss_weight needs --loc_loss iou, giou, diou or ciou')
     given = [n for n in ('focal_alpha', 'focal_gamma') if getattr(F, n) is not None]
     if F.focal_alpha is None:
         F.focal_alpha = 0.25
@@ -218,11 +239,17 @@ def main(argv=None):
                       reducer=make_reducer(world, rank) if world > 1 else None, backbone_name=F.backbone_name,
                       sync_bn=F.sync_bn, momentum=F.momentum, nesterov=F.nesterov, weight_decay=F.weight_decay,
                       clip_norm=F.clip_norm, warmup_steps=F.warmup_steps, fix_learning_rate=F.fix_learning_rate,
-                      clf_loss=F.clf_loss, focal_alpha=F.focal_alpha, focal_gamma=F.focal_gamma)
+                      clf_loss=F.clf_loss, focal_alpha=F.focal_alpha, focal_gamma=F.focal_gamma,
+                      loc_loss=F.loc_loss, loc_loss_weight=F.loc_loss_weight)
     if tr_range is config.train_range.ALL:
         logger.info('Classifier loss: %s' % ('focal loss, alpha=%g gamma=%g (no hard-negative mining, no IoU factor)'
                                               % (F.focal_alpha, F.focal_gamma) if F.clf_loss == 'focal'
                                               else 'softmax cross-entropy with 3:1 hard-negative mining'))
+    if tr_range is config.train_range.ALL:
+        logger.info('Box regression loss: %s' % ('%s loss on the decoded boxes, weight %g (no smooth-L1)'
+                                                 % ({'iou': 'IoU', 'giou': 'GIoU', 'diou': 'DIoU', 'ciou': 'CIoU'}
+                                                    [F.loc_loss], F.loc_loss_weight) if F.loc_loss != 'smooth_l1'
+                                                 else 'masked smooth-L1 on the encoded offsets'))
     store = trainer.net.store
     logger.info('Total trainable parameters:%s' % str(store.trainable_count()))
     step0 = 0

@@ -353,6 +353,7 @@ def det_groundtruth(refine_out, offset_gt, cbboxes, refine_labels, refine_pos_ma
                         tab.split(iou, 0))
     res.flat = (det_gt, det_pos, det_lbl, iou)
     res.table = tab
+    res.cbox, res.refine_flat = cbox, ro      # what an IoU-family box loss reads (det_clf_loss)
     return res
 
 
@@ -363,7 +364,8 @@ HNM_EXCHANGE = None
 
 
 def det_clf_loss(refine_out, clf_out, det_out, det_groundtruth, det_pos_mask, det_labels, iou_all_layers,
-                 dtype=torch.float32, scale=None, targets=None, clf_loss='hnm', focal_alpha=0.25, focal_gamma=2.0):
+                 dtype=torch.float32, scale=None, targets=None, clf_loss='hnm', focal_alpha=0.25, focal_gamma=2.0,
+                 loc_loss='smooth_l1', loc_loss_weight=1.0, refine_flat=None):
     """(det_loss, clf_loss) (net_tools.py:519-623): masked smooth-L1 on the ODM offsets and
     softmax cross-entropy with global hard-negative mining and the IoU focal factor.
 
@@ -374,11 +376,21 @@ def det_clf_loss(refine_out, clf_out, det_out, det_groundtruth, det_pos_mask, de
     gradient reaches refine_out through it.  last_stats is then [pos_loss, neg_loss, clf_loss, 0,
     n_pos, 0, n_neg, norm].  The smooth-L1 loss is the same in both modes.
 
+    loc_loss='iou' | 'giou' | 'diou' | 'ciou' (opt-in; the reference has none) replaces the smooth-L1
+    by that loss between the box the ODM predicts, decode(anchor, refine_out + det_out), and the
+    matched box, over det_pos, times loc_loss_weight (rod_box_iou_loss; smooth-L1 is not launched).
+    det_loss and last_det_per_layer keep their meaning (total and [L+1] per-level values).  The
+    prediction depends on refine_out: `refine_flat` is the concatenated refine_out this loss reads
+    (its own alias of a fork when the refine net is trained; default: the one det_groundtruth()
+    read, which is right whenever refine_out carries no gradient).
+
     `det_groundtruth` may be the object returned by det_groundtruth() (fast path).  The
     summaries the reference logs (pos/neg/clf loss, max hard prediction, positives) are
     left in det_clf_loss.last_stats ([8] device tensor, see rod_softmax_ce_hnm)."""
     if clf_loss not in ('hnm', 'focal'):
         raise ValueError("clf_loss must be 'hnm' or 'focal', got %r" % (clf_loss,))
+    if loc_loss != 'smooth_l1' and loc_loss not in ops.BOX_LOSS_KINDS:
+        raise ValueError("loc_loss must be 'smooth_l1', 'iou', 'giou', 'diou' or 'ciou', got %r" % (loc_loss,))
     B = clf_out[0].shape[0]
     scale = float(B) if scale is None else float(scale)
     tg = det_groundtruth if isinstance(det_groundtruth, RefineTargets) and hasattr(det_groundtruth, 'flat') \
@@ -388,7 +400,11 @@ def det_clf_loss(refine_out, clf_out, det_out, det_groundtruth, det_pos_mask, de
     det_gt, det_pos, det_lbl, iou = tg.flat
     lvl_off = tg.table.lvl_off
     pred = ops.levels_concat(det_out, 4)
-    dvec, det_loss_one = ops.smooth_l1_masked(pred, det_gt, det_pos, lvl_off, scale)
+    if loc_loss == 'smooth_l1':
+        dvec, det_loss_one = ops.smooth_l1_masked(pred, det_gt, det_pos, lvl_off, scale)
+    else:
+        dvec, det_loss_one = ops.box_iou_loss(tg.table.center, tg.refine_flat if refine_flat is None else refine_flat,
+                                              pred, tg.cbox, det_pos, lvl_off, loc_loss, loc_loss_weight, scale)
     logits = ops.levels_concat(clf_out, config.total_obj_n)
     if clf_loss == 'focal':        # data parallel: the positives of the global batch
         if HNM_EXCHANGE is not None:
