@@ -23,12 +23,13 @@
 #define ROD_H_
 
 #include <stddef.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-#define ROD_ABI_VERSION 27
+#define ROD_ABI_VERSION 28
 #define ROD_EINVAL (-1)
 
 enum { ROD_F32 = 0, ROD_BF16 = 1, ROD_I32 = 2 /* collectives only (ABI 19) */ };
@@ -752,6 +753,42 @@ int rod_select_topk_softnms(const float* probs, const float* boxes, int B, int A
                             float select_threshold, int top_k, int keep_top_k, float nms_threshold,
                             int method, float sigma, float min_score, float* out_scores,
                             float* out_boxes, void* workspace, void* stream);
+
+/* ------------------------------------------------ evaluation: TP/FP matching (ABI 28; opt-in)
+ * bboxes_matching (tf_extended/bboxes.py:246-334) of the score-ordered detections of every image
+ * b and class slot c (label = first_label + c) against the image's ground truth, at T IoU
+ * thresholds in one launch — the reference's rule run once per threshold, bit for bit.
+ * det_scores [B,C,N] and det_boxes [B,C,N,4] are the outputs of rod_select_topk_nms /
+ * rod_select_topk_softnms (corner boxes, score order); gt_labels [B,G], gt_boxes [B,G,4] corner,
+ * gt_difficult [B,G] (NULL: none difficult), gt_count [B] (clamped to [0, G]); rows >=
+ * gt_count[b] are padding and are never read.  thresholds [T] is a DEVICE fp32 array.
+ * det_boxes and gt_boxes are 16-byte aligned.  For every (b, c), with g = gt_count[b]:
+ *   n_gt[b,c]   the number of j < g with label_j == label and not difficult.
+ *   g == 0      every detection i < N gets tp = 0 and fp = 1 in all T bits.
+ *   otherwise   per detection i, jac_ij for j < g: the IoU of bboxes_jaccard (bboxes.py:452-479),
+ *               each line one fp32 operation rounded on its own, no contraction:
+ *                 h = max(min(g_ymax, d_ymax) - max(g_ymin, d_ymin), 0)      (w likewise, on x)
+ *                 inter = h * w
+ *                 union = ((-inter + area_g) + area_det)        area = (ymax - ymin) * (xmax - xmin)
+ *                 iou = union > 0 ? inter / union : 0                       (IEEE division)
+ *                 jac = iou * (label_j == label ? 1.0f : 0.0f)
+ *               idx_i = the FIRST maximum of jac_ij over j < g (all 0: ground truth 0, whatever
+ *               its label — the reference's quirk, kept); nd_i = !difficult[idx_i];
+ *               match_it = jac_i,idx > thresholds[t]  (strict, fp32);
+ *               tp_it = nd_i && match_it && no i' < i has idx_i' == idx_i && nd_i' && match_i't
+ *               fp_it = nd_i && !tp_it
+ *   output      bit t of tp_mask[b,c,i] / fp_mask[b,c,i] = tp_it / fp_it; the other bits are 0.
+ * The ground truth a detection competes for does not depend on the threshold or on what was
+ * matched before it, so "already matched" reduces to "an earlier detection matches the same box
+ * at t": one workgroup per (b, c) takes an integer min per (box, threshold) in LDS — no sequential
+ * loop, deterministic.  Zero-padded detections (score 0, zero box) are processed like any other;
+ * no decision reads det_scores (it may be NULL) — the caller filters rows on score.
+ * Limits, checked before any HIP call: 1 <= T <= 16, 1 <= N <= 1024, 0 <= G <= 512, B <= 65535,
+ * thresholds != NULL.  No workspace, no allocation, no host synchronisation: capturable. */
+int rod_match_detections(const float* det_scores, const float* det_boxes, const int32_t* gt_labels,
+                         const float* gt_boxes, const uint8_t* gt_difficult, const int32_t* gt_count,
+                         const float* thresholds, int B, int C, int N, int G, int T, int first_label,
+                         int32_t* tp_mask, int32_t* fp_mask, int32_t* n_gt, void* stream);
 
 /* ------------------------------------------------ optimiser (A14)
  * Plain SGD with clip by value (net_tools.py:645-651):

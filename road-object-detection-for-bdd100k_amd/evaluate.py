@@ -5,6 +5,15 @@ detected_bboxes (per-class select / top-k / NMS, one kernel) -> TP/FP matching a
 ground truth -> streaming TP/FP arrays -> VOC07 / VOC12 AP per class and their mean, over
 ceil(3000 / batch_size) batches (evaluate.py:219).  Matching and AP are host code, as the
 reference pins them to the CPU (evaluate.py:146, 164).
+
+Opt-in (not in the reference): --match_on device matches on the GPU (rod_match_detections) and
+keeps the TP/FP masks there until the end of the run — one device -> host copy instead of one
+per batch; --ap_iou_sweep evaluates AP at several matching IoU thresholds from that one launch
+per batch.  At every threshold the rule is the reference's own matching rule (bboxes_matching:
+first argmax of IoU over same-label boxes, strict comparison, one TP per ground truth), not
+pycocotools' rule, and AP is this project's VOC12 area / VOC07 11-point value — the mean over the
+sweep is a mean of those, not the COCO metric.  Without the new flags the run, its printout and
+eval.json are today's.
 """
 import argparse
 import math
@@ -54,7 +63,61 @@ def parse(argv=None):
     ap.add_argument('--synthetic', type=str2bool, default=False,
                     help='run on synthetic BDD-shaped batches (no dataset needed); results are not real '
                          'metrics.  Without it a missing dataset or checkpoint is an error')
-    return ap.parse_args(argv)
+    ap.add_argument('--match_on', default=None, choices=['host', 'device'],
+                    help="where detections are matched with the ground truth (default host: the reference's "
+                         'per-batch host loop).  device: one HIP kernel per batch, TP/FP kept on the GPU, one '
+                         'copy to the host at the end of the run; same matching rule, same AP')
+    ap.add_argument('--ap_iou_sweep', default='',
+                    help="also report AP at these matching IoU thresholds: 'coco' = 0.50:0.05:0.95 (10 values), or "
+                         "a comma list such as 0.5,0.75.  Implies --match_on device.  Each threshold applies the "
+                         "reference's matching rule (not pycocotools' rule) and AP stays this project's VOC12 area "
+                         '/ VOC07 11-point value; at most %d distinct thresholds with --matching_threshold'
+                         % MAX_THRESHOLDS)
+    F = ap.parse_args(argv)
+    try:
+        F.sweep_thresholds = parse_iou_sweep(F.ap_iou_sweep)
+    except ValueError as e:
+        ap.error('--ap_iou_sweep: %s' % e)
+    if F.sweep_thresholds.size:
+        if F.match_on == 'host':
+            ap.error('--ap_iou_sweep needs --match_on device (the host loop matches at one threshold)')
+        F.match_on = 'device'
+    elif F.match_on is None:
+        F.match_on = 'host'
+    # bit 0 of the device masks is --matching_threshold (today's AP outputs); the sweep values follow
+    base = np.float32(F.matching_threshold)
+    F.match_thresholds = np.concatenate([[base], F.sweep_thresholds[F.sweep_thresholds != base]]).astype(np.float32)
+    if F.match_thresholds.size > MAX_THRESHOLDS:
+        ap.error('--ap_iou_sweep: %d distinct thresholds with --matching_threshold, at most %d'
+                 % (F.match_thresholds.size, MAX_THRESHOLDS))
+    return F
+
+
+MAX_THRESHOLDS = 16   # bits of rod_match_detections' masks (include/rod.h)
+
+
+def parse_iou_sweep(text):
+    """'' -> no sweep; 'coco' -> np.linspace(0.5, 0.95, 10) as float32; else a comma list of
+    thresholds in [0, 1), duplicates dropped, order kept.  float32 [n]."""
+    text = text.strip()
+    if not text:
+        return np.zeros(0, np.float32)
+    if text == 'coco':
+        return np.linspace(0.5, 0.95, 10).astype(np.float32)
+    vals = []
+    for tok in text.split(','):
+        v = np.float32(float(tok))    # ValueError on a malformed number
+        if not 0 <= v < 1:
+            raise ValueError('threshold %r is outside [0, 1)' % tok)
+        if v not in vals:
+            vals.append(v)
+    return np.array(vals, np.float32)
+
+
+def iou_key(t):
+    """eval.json key of a threshold: two decimals ('0.50') when that names it exactly."""
+    s = '%.2f' % t
+    return s if np.float32(s) == np.float32(t) else repr(float(t))
 
 
 def latest_checkpoint(path, backbone):
@@ -108,6 +171,11 @@ def main(argv=None):
     num_batches = math.ceil(F.num_images / float(F.batch_size))
     state = None
     classes = list(range(1, config.total_obj_n))
+    on_device = F.match_on == 'device'
+    if on_device:
+        from rod import ops
+        acc = tfe.SweepTPFP(F.match_thresholds, len(classes), num_batches * F.batch_size, F.keep_top_k, dev,
+                            first_label=classes[0])
     start = time.time()
     with torch.no_grad():
         for _ in range(num_batches):
@@ -117,6 +185,14 @@ def main(argv=None):
                                                    net=net).get_output()
             probs = net_tools.class_probabilities(clf_out)
             boxes = net_tools.decode_all_layers(anchors_all, refine_out, det_out, to_corner=True)
+            if on_device:   # nothing of the batch leaves the GPU
+                pscores, pboxes = net_tools.detected_bboxes_packed(
+                    probs, boxes, select_threshold=F.select_threshold, nms_threshold=F.nms_threshold,
+                    top_k=F.select_top_k, keep_top_k=F.keep_top_k, nms_method=F.nms_method,
+                    soft_nms_sigma=F.soft_nms_sigma, soft_nms_min_score=F.soft_nms_min_score)
+                acc.update(pscores, *ops.match_detections(pscores, pboxes, glabels, gboxes, gn, acc.thresholds_dev,
+                                                          first_label=classes[0]))
+                continue
             rscores, rbboxes = net_tools.detected_bboxes(probs, boxes, select_threshold=F.select_threshold,
                                                          nms_threshold=F.nms_threshold, top_k=F.select_top_k,
                                                          keep_top_k=F.keep_top_k, nms_method=F.nms_method,
@@ -129,8 +205,11 @@ def main(argv=None):
                                                        matching_threshold=F.matching_threshold, gt_counts=gcount)
             state = tfe.streaming_tp_fp_arrays(n_g, tp, fp, rs, state=state)
     aps07, aps12 = {}, {}
+    if on_device:
+        per_threshold = acc.value()       # the run's one device -> host copy
+        by07, by12 = acc.average_precisions(per_threshold)
     for c in classes:
-        prec, rec = tfe.precision_recall(*state[c].value())
+        prec, rec = tfe.precision_recall(*(per_threshold[0][c] if on_device else state[c].value()))
         aps07[c] = tfe.average_precision_voc07(prec, rec)
         aps12[c] = tfe.average_precision_voc12(prec, rec)
         logger.info('AP_VOC07/%d %.6f  AP_VOC12/%d %.6f' % (c, aps07[c], c, aps12[c]))
@@ -140,15 +219,32 @@ def main(argv=None):
         logger.warning('--synthetic: the AP values below are over synthetic ground truth, not a BDD100K result')
     print('AP_VOC07/mAP[%s]' % mAP07)
     print('AP_VOC12/mAP[%s]' % mAP12)
+    extra = {}
+    if F.sweep_thresholds.size:
+        bits = [int(np.nonzero(F.match_thresholds == t)[0][0]) for t in F.sweep_thresholds]
+        keys = [iou_key(t) for t in F.sweep_thresholds]
+        mean = lambda d: sum(d.values()) / len(d)  # noqa: E731
+        extra = {'iou_thresholds': [float(t) for t in F.sweep_thresholds],
+                 'AP_VOC07_by_iou': {k: by07[b] for k, b in zip(keys, bits)},
+                 'AP_VOC12_by_iou': {k: by12[b] for k, b in zip(keys, bits)},
+                 'mAP_VOC07_by_iou': {k: mean(by07[b]) for k, b in zip(keys, bits)},
+                 'mAP_VOC12_by_iou': {k: mean(by12[b]) for k, b in zip(keys, bits)}}
+        extra['mAP_VOC07_sweep'] = mean(extra['mAP_VOC07_by_iou'])
+        extra['mAP_VOC12_sweep'] = mean(extra['mAP_VOC12_by_iou'])
+        for k in keys:
+            print('IoU>%s  AP_VOC07/mAP[%s]  AP_VOC12/mAP[%s]' % (k, extra['mAP_VOC07_by_iou'][k],
+                                                                 extra['mAP_VOC12_by_iou'][k]))
+        print('IoU sweep mean (reference matching rule, VOC AP)  AP_VOC07/mAP[%s]  AP_VOC12/mAP[%s]'
+              % (extra['mAP_VOC07_sweep'], extra['mAP_VOC12_sweep']))
     elapsed = time.time() - start
     print('Time spent : %.3f seconds.' % elapsed)
     print('Time spent per BATCH: %.3f seconds.' % (elapsed / num_batches))
     os.makedirs(F.eval_dir, exist_ok=True)
     with open(os.path.join(F.eval_dir, 'eval.json'), 'w') as f:
         import json
-        json.dump({'AP_VOC07': aps07, 'AP_VOC12': aps12, 'mAP_VOC07': mAP07, 'mAP_VOC12': mAP12,
-                   'num_batches': num_batches, 'seconds': elapsed, 'synthetic': bool(F.synthetic),
-                   'checkpoint': ckpt}, f)
+        json.dump(dict({'AP_VOC07': aps07, 'AP_VOC12': aps12, 'mAP_VOC07': mAP07, 'mAP_VOC12': mAP12,
+                        'num_batches': num_batches, 'seconds': elapsed, 'synthetic': bool(F.synthetic),
+                        'checkpoint': ckpt}, **extra), f)
     return mAP07, mAP12
 
 

@@ -1993,6 +1993,29 @@ def select_topk_soft_nms(probs, boxes, select_threshold, top_k, keep_top_k, nms_
     return scores, bxs
 
 
+def match_detections(scores, boxes, glabels, gboxes, gcount, thresholds, gdifficult=None, first_label=1):
+    """rod_match_detections: TP/FP matching of the packed detections (scores [B, C, N], boxes
+    [B, C, N, 4], the outputs of select_topk_nms / select_topk_soft_nms; class slot c has label
+    first_label + c) against the ground truth (glabels [B, G], gboxes [B, G, 4] corner, gcount
+    [B], gdifficult [B, G] or None) at the IoU thresholds of the device fp32 vector `thresholds`
+    [T] (semantics in include/rod.h).  Returns (tp_mask, fp_mask) int32 [B, C, N] — bit t =
+    threshold t — and n_gt int32 [B, C].  Device tensors in, device tensors out, no sync."""
+    B, C, N = scores.shape
+    G = glabels.shape[1]
+    dev = scores.device
+    if thresholds.device != dev or thresholds.dtype != torch.float32:
+        raise ValueError('match_detections: thresholds must be a float32 tensor on %s' % (dev,))
+    i32 = lambda t: t.to(torch.int32).contiguous()  # noqa: E731
+    gd = None if gdifficult is None else gdifficult.to(torch.uint8).contiguous()
+    tp = torch.empty((B, C, N), dtype=torch.int32, device=dev)
+    fp = torch.empty((B, C, N), dtype=torch.int32, device=dev)
+    n_gt = torch.empty((B, C), dtype=torch.int32, device=dev)
+    _abi.call("rod_match_detections", scores.contiguous(), boxes.float().contiguous(), i32(glabels),
+              gboxes.float().contiguous(), gd, i32(gcount), thresholds.contiguous(), B, C, N, G,
+              int(thresholds.numel()), int(first_label), tp, fp, n_gt, stream())
+    return tp, fp, n_gt
+
+
 # ----------------------------------------------------------------------------- VGG-16 ops (F3)
 # slim.conv2d with activation_fn and no normaliser (vgg_arg_scope: relu, nets/backbone/vgg.py:58):
 # the conv's output y is left as an owned Pending with an identity BatchNorm (mean 0, rstd 1,

@@ -445,6 +445,24 @@ def class_probabilities(clf_out):
     return ops.softmax(logits, config.total_obj_n)
 
 
+def detected_bboxes_packed(predictions, localisations, select_threshold=None, nms_threshold=0.5, top_k=800,
+                           keep_top_k=200, nms_method='hard', soft_nms_sigma=0.5, soft_nms_min_score=0.001):
+    """detected_bboxes without the per-class dicts: the kernel's packed outputs, scores
+    [B, K-1, keep_top_k] and boxes [B, K-1, keep_top_k, 4] (class slot c - 1 = class c), as
+    rod.ops.match_detections takes them.  Same arguments as detected_bboxes."""
+    if nms_method not in ('hard', 'linear', 'gaussian'):
+        raise ValueError("nms_method must be 'hard', 'linear' or 'gaussian', got %r" % (nms_method,))
+    if isinstance(predictions, (list, tuple)):
+        predictions = ops.levels_concat([p.float() for p in predictions], config.total_obj_n)
+    if isinstance(localisations, (list, tuple)):
+        localisations = ops.levels_concat([l.float() for l in localisations], 4)
+    thr = 0.0 if select_threshold is None else select_threshold
+    if nms_method == 'hard':
+        return ops.select_topk_nms(predictions, localisations, thr, top_k, keep_top_k, nms_threshold)
+    return ops.select_topk_soft_nms(predictions, localisations, thr, top_k, keep_top_k, nms_threshold, nms_method,
+                                    soft_nms_sigma, soft_nms_min_score)
+
+
 def detected_bboxes(predictions, localisations, select_threshold=None, nms_threshold=0.5, clipping_bbox=None,
                     top_k=800, keep_top_k=200, nms_method='hard', soft_nms_sigma=0.5, soft_nms_min_score=0.001):
     """Per-class select -> top_k -> NMS -> pad (net_tools.py:739-758) in one kernel.
@@ -456,21 +474,11 @@ def detected_bboxes(predictions, localisations, select_threshold=None, nms_thres
     returned scores are the rescored ones, emission stops below soft_nms_min_score; 'gaussian'
     uses soft_nms_sigma and ignores nms_threshold).
     Returns dicts {c: scores [B, keep_top_k]}, {c: boxes [B, keep_top_k, 4]} for c = 1..K-1."""
-    if nms_method not in ('hard', 'linear', 'gaussian'):
-        raise ValueError("nms_method must be 'hard', 'linear' or 'gaussian', got %r" % (nms_method,))
-    if isinstance(predictions, (list, tuple)):
-        predictions = ops.levels_concat([p.float() for p in predictions], config.total_obj_n)
-    if isinstance(localisations, (list, tuple)):
-        localisations = ops.levels_concat([l.float() for l in localisations], 4)
-    thr = 0.0 if select_threshold is None else select_threshold
-    if nms_method == 'hard':
-        scores, boxes = ops.select_topk_nms(predictions, localisations, thr, top_k, keep_top_k, nms_threshold)
-    else:
-        scores, boxes = ops.select_topk_soft_nms(predictions, localisations, thr, top_k, keep_top_k, nms_threshold,
-                                                 nms_method, soft_nms_sigma, soft_nms_min_score)
+    scores, boxes = detected_bboxes_packed(predictions, localisations, select_threshold, nms_threshold, top_k,
+                                           keep_top_k, nms_method, soft_nms_sigma, soft_nms_min_score)
     if clipping_bbox is not None:
         raise NotImplementedError('clipping_bbox is never used by the reference CLIs (predict.py:136)')
-    K = predictions.shape[-1]
+    K = scores.shape[1] + 1
     return ({c: scores[:, c - 1] for c in range(1, K)}, {c: boxes[:, c - 1] for c in range(1, K)})
 
 

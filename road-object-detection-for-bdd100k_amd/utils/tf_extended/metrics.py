@@ -1,10 +1,12 @@
 """utils/tf_extended/metrics.py — streaming TP/FP arrays, precision/recall, VOC07/VOC12 AP
-(metrics.py:100-258), host numpy float64 as in the reference."""
+(metrics.py:100-258), host numpy float64 as in the reference.  SweepTPFP (opt-in, not in the
+reference) accumulates the device matcher's per-threshold TP/FP bit masks on the device and
+applies the same host rules once, at the end of the run."""
 import numpy as np
 
 from utils.tf_extended.math import cummax
 
-__all__ = ['streaming_tp_fp_arrays', 'StreamingTPFP', 'precision_recall', 'average_precision_voc07',
+__all__ = ['streaming_tp_fp_arrays', 'StreamingTPFP', 'SweepTPFP', 'precision_recall', 'average_precision_voc07',
            'average_precision_voc12']
 
 
@@ -48,6 +50,77 @@ def streaming_tp_fp_arrays(num_gbboxes, tp, fp, scores, remove_zero_scores=True,
     st = StreamingTPFP(remove_zero_scores) if state is None else state
     st.update(num_gbboxes, tp, fp, scores)
     return st
+
+
+class SweepTPFP(object):
+    """Device-resident accumulator of rod.ops.match_detections outputs over a run, for every
+    class slot c (label first_label + c) and every threshold t (bit t of the masks).
+
+    One preallocated int32 buffer [capacity_images, C, 3 * N + 1] holds, per image and class,
+    the N scores (their fp32 bits), the N tp masks, the N fp masks and n_gt.  update() copies a
+    batch's tensors into the next rows on the current stream — no host synchronisation;
+    value() makes ONE device -> host copy of the filled rows and then, per threshold and class,
+    applies StreamingTPFP's rule (rows with tp or fp and score > 1e-4 are kept, in batch order)
+    to give the reference's metric tuple for precision_recall / average_precision_voc07 / 12.
+    Everything after the copy is host numpy, as in the reference."""
+
+    def __init__(self, thresholds, num_classes, capacity_images, keep_top_k, device, first_label=1,
+                 remove_zero_scores=True):
+        import torch
+        self.thresholds = np.array(thresholds, np.float32).reshape(-1)
+        if not 1 <= self.thresholds.size <= 16:
+            raise ValueError('SweepTPFP: 1 to 16 thresholds (the bits of the masks), got %d' % self.thresholds.size)
+        self.C, self.N, self.capacity = int(num_classes), int(keep_top_k), int(capacity_images)
+        self.first_label = int(first_label)
+        self.remove_zero_scores = remove_zero_scores
+        self.device = torch.device(device)
+        self.thresholds_dev = torch.from_numpy(self.thresholds.copy()).to(self.device)
+        self.buf = torch.zeros((self.capacity, self.C, 3 * self.N + 1), dtype=torch.int32, device=self.device)
+        self.count = 0
+
+    def update(self, scores, tp_mask, fp_mask, n_gt):
+        """scores fp32 [B, C, N], tp_mask / fp_mask int32 [B, C, N], n_gt int32 [B, C]."""
+        import torch
+        B, N = scores.shape[0], self.N
+        if tuple(scores.shape) != (B, self.C, N) or tuple(n_gt.shape) != (B, self.C):
+            raise ValueError('SweepTPFP.update: expected [B, %d, %d] scores, got %s' % (self.C, N, tuple(scores.shape)))
+        if scores.dtype != torch.float32:
+            raise ValueError('SweepTPFP.update: scores must be float32')
+        if self.count + B > self.capacity:
+            raise ValueError('SweepTPFP.update: capacity of %d images exceeded' % self.capacity)
+        rows = self.buf[self.count:self.count + B]
+        rows[:, :, :N].copy_(scores.contiguous().view(torch.int32))
+        rows[:, :, N:2 * N].copy_(tp_mask)
+        rows[:, :, 2 * N:3 * N].copy_(fp_mask)
+        rows[:, :, 3 * N].copy_(n_gt)
+        self.count += B
+
+    def value(self):
+        """[{label: (num_gbboxes, num_detections, tp, fp, scores)} for each threshold]: the
+        tuples StreamingTPFP.value() gives after the same batches at that threshold."""
+        N = self.N
+        host = self.buf[:self.count].cpu().numpy()          # the run's only device -> host copy
+        scores = np.ascontiguousarray(host[:, :, :N]).view(np.float32)
+        tpm, fpm, n_gt = host[:, :, N:2 * N], host[:, :, 2 * N:3 * N], host[:, :, 3 * N]
+        out = []
+        for t in range(self.thresholds.size):
+            per = {}
+            for c in range(self.C):
+                st = StreamingTPFP(self.remove_zero_scores)
+                st.update(n_gt[:, c], (tpm[:, c] >> t) & 1, (fpm[:, c] >> t) & 1, scores[:, c])
+                per[self.first_label + c] = st.value()
+            out.append(per)
+        return out
+
+    def average_precisions(self, value=None):
+        """([{label: AP_VOC07}], [{label: AP_VOC12}]), one dict per threshold."""
+        value = self.value() if value is None else value
+        ap07, ap12 = [], []
+        for per in value:
+            pr = {c: precision_recall(*v) for c, v in per.items()}
+            ap07.append({c: average_precision_voc07(*v) for c, v in pr.items()})
+            ap12.append({c: average_precision_voc12(*v) for c, v in pr.items()})
+        return ap07, ap12
 
 
 def _safe_div(a, b):
