@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ROD_ABI_VERSION 28
+#define ROD_ABI_VERSION 29
 #define ROD_EINVAL (-1)
 
 enum { ROD_F32 = 0, ROD_BF16 = 1, ROD_I32 = 2 /* collectives only (ABI 19) */ };
@@ -838,6 +838,28 @@ int rod_grad_sqnorm(const float* grad, const unsigned char* flags, long n, float
 int rod_sgd_momentum(float* param, const float* grad, float* mom, const unsigned char* flags, long n,
                      const float* lr, const float* scale, float mu, float wd, float clip,
                      int nesterov, void* stream);
+
+/* Momentum SGD with an exponential moving average of the weights kept in the same pass (ABI 29;
+ * tf.train.ExponentialMovingAverage, which the reference does not use: opt-in).
+ *
+ * rod_sgd_momentum_ema: per element of a trainable group, exactly the lines of rod_sgd_momentum in
+ * their order, then, with p the value just written and e the element of the shadow buffer `ema`,
+ * three more lines, each one fp32 operation rounded on its own:
+ *     t = e - p
+ *     t = *ema_rate * t                    ema_rate = 1 - decay
+ *     e = e - t
+ * (TF's variable -= (1 - decay) * (variable - value)).  ema_rate is read from device memory like
+ * lr: a captured graph applies whatever the host last wrote (the num_updates warm-up is a host
+ * schedule).  One launch, the grid of rod_sgd_momentum; per trainable group one flag byte, four
+ * 16-byte loads and three 16-byte stores (one load and one store fewer with mom == NULL).
+ * Groups without ROD_OPT_TRAINABLE are not touched: none of param, mom, ema is read or written,
+ * whatever grad or ema hold there.  mom == NULL is allowed when mu == 0 and scale == NULL means
+ * no norm clipping, as in rod_sgd_momentum; ema, ema_rate and lr are required.  param, grad, mom
+ * and ema are 16-byte aligned and do not overlap. */
+int rod_sgd_momentum_ema(float* param, const float* grad, float* mom, float* ema,
+                         const unsigned char* flags, long n, const float* lr, const float* scale,
+                         const float* ema_rate, float mu, float wd, float clip, int nesterov,
+                         void* stream);
 
 /* ------------------------------------------------ deferred parameter-gradient sums (ABI 11)
  * The weight / bias gradients of rod_conv_wgrad, rod_dw3x3_bwd_filter(_bn) and rod_pw_bwd end in

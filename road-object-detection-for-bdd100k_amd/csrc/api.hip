@@ -248,14 +248,21 @@ __global__ void sgd_clip_kernel(float* __restrict__ p, const float* __restrict__
 // contract in include/rod.h; -ffp-contract=off keeps every line one rounded operation).
 // One thread per group of 4 elements per pass: one flag byte, three 16-byte loads, two 16-byte
 // stores.  A group without ROD_OPT_TRAINABLE costs its flag byte only.
+// EMA (rod_sgd_momentum_ema): the shadow e follows the p just written, e = e - rate * (e - p) in
+// three rounded operations; one more 16-byte load and store per trainable group.  EMA = false
+// never reads e or rate_p (both NULL there) and is the kernel rod_sgd_momentum always launched.
+template <bool EMA>
 __global__ void __launch_bounds__(256) sgd_momentum_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                           float* __restrict__ m,
+                                                           float* __restrict__ m, float* __restrict__ e,
                                                            const uint8_t* __restrict__ flags, long ngroups,
                                                            const float* __restrict__ lr_p,
-                                                           const float* __restrict__ scale_p, float mu, float wd,
+                                                           const float* __restrict__ scale_p,
+                                                           const float* __restrict__ rate_p, float mu, float wd,
                                                            float clip, int nesterov) {
   const float lr = *lr_p;
   const float scale = scale_p ? *scale_p : 1.0f;
+  float rate = 0.0f;
+  if constexpr (EMA) rate = *rate_p;
   long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long stride = (long)gridDim.x * blockDim.x;
   for (; q < ngroups; q += stride) {
@@ -266,6 +273,8 @@ __global__ void __launch_bounds__(256) sgd_momentum_kernel(float* __restrict__ p
     const f32x4 gv = *(const f32x4*)(g + i);
     f32x4 mv = {0.0f, 0.0f, 0.0f, 0.0f};
     if (m) mv = *(f32x4*)(m + i);
+    f32x4 ev = {0.0f, 0.0f, 0.0f, 0.0f};
+    if constexpr (EMA) ev = *(f32x4*)(e + i);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float d = gv[j];
@@ -276,9 +285,15 @@ __global__ void __launch_bounds__(256) sgd_momentum_kernel(float* __restrict__ p
       const float u = nesterov ? d + mu * mj : mj;
       pv[j] = pv[j] - lr * u;
       mv[j] = mj;
+      if constexpr (EMA) {
+        float t = ev[j] - pv[j];                       // tf.train.ExponentialMovingAverage:
+        t = rate * t;                                  // variable -= (1 - decay) * (variable - value)
+        ev[j] = ev[j] - t;
+      }
     }
     *(f32x4*)(p + i) = pv;
     if (m) *(f32x4*)(m + i) = mv;
+    if constexpr (EMA) *(f32x4*)(e + i) = ev;
   }
 }
 
@@ -479,9 +494,32 @@ int rod_sgd_momentum(float* param, const float* grad, float* mom, const unsigned
                 "rod_sgd_momentum: param, grad and flags are required");
   const long ngroups = n / 4;
   int blocks = (int)std::min<long>(cdivl(ngroups, 256), 4096);
-  hipLaunchKernelGGL(sgd_momentum_kernel, dim3(blocks), dim3(256), 0, ROD_STREAM(stream), param, grad, mom,
-                     (const uint8_t*)flags, ngroups, lr, scale, mu, wd, clip, nesterov);
+  hipLaunchKernelGGL(sgd_momentum_kernel<false>, dim3(blocks), dim3(256), 0, ROD_STREAM(stream), param, grad, mom,
+                     (float*)nullptr, (const uint8_t*)flags, ngroups, lr, scale, (const float*)nullptr, mu, wd, clip,
+                     nesterov);
   return check_launch("rod_sgd_momentum");
+}
+
+int rod_sgd_momentum_ema(float* param, const float* grad, float* mom, float* ema, const unsigned char* flags,
+                         long n, const float* lr, const float* scale, const float* ema_rate, float mu, float wd,
+                         float clip, int nesterov, void* stream) {
+  ROD_CHECK_ARG(n >= 0 && n % 4 == 0, "rod_sgd_momentum_ema: n must be a non-negative multiple of 4");
+  ROD_CHECK_ARG(((uintptr_t)param & 15) == 0 && ((uintptr_t)grad & 15) == 0 && ((uintptr_t)mom & 15) == 0 &&
+                    ((uintptr_t)ema & 15) == 0,
+                "rod_sgd_momentum_ema: buffers must be 16-byte aligned");
+  ROD_CHECK_ARG(ema != nullptr && ema_rate != nullptr,
+                "rod_sgd_momentum_ema: ema and ema_rate (device pointer) are required");
+  ROD_CHECK_ARG(lr != nullptr, "rod_sgd_momentum_ema: lr (device pointer) is required");
+  ROD_CHECK_ARG(mom != nullptr || mu == 0.0f, "rod_sgd_momentum_ema: mu != 0 needs the momentum buffer");
+  ROD_CHECK_ARG(!(clip < 0.0f) && clip == clip, "rod_sgd_momentum_ema: clip must be >= 0 (+inf disables it)");
+  if (n == 0) return 0;
+  ROD_CHECK_ARG(param != nullptr && grad != nullptr && flags != nullptr,
+                "rod_sgd_momentum_ema: param, grad and flags are required");
+  const long ngroups = n / 4;
+  int blocks = (int)std::min<long>(cdivl(ngroups, 256), 4096);
+  hipLaunchKernelGGL(sgd_momentum_kernel<true>, dim3(blocks), dim3(256), 0, ROD_STREAM(stream), param, grad, mom,
+                     ema, (const uint8_t*)flags, ngroups, lr, scale, ema_rate, mu, wd, clip, nesterov);
+  return check_launch("rod_sgd_momentum_ema");
 }
 
 }  // extern "C"

@@ -73,6 +73,9 @@ def parse(argv=None):
                          "reference's matching rule (not pycocotools' rule) and AP stays this project's VOC12 area "
                          '/ VOC07 11-point value; at most %d distinct thresholds with --matching_threshold'
                          % MAX_THRESHOLDS)
+    ap.add_argument('--use_ema', type=str2bool, default=False,
+                    help='evaluate the averaged weights the checkpoint holds (train.py --ema_decay) in place of '
+                         'the variables; an error if it holds none')
     F = ap.parse_args(argv)
     try:
         F.sweep_thresholds = parse_iou_sweep(F.ap_iou_sweep)
@@ -157,8 +160,8 @@ def main(argv=None):
     ckpt = latest_checkpoint(F.checkpoint_path, F.backbone_name)
     if ckpt is not None:
         from rod.checkpoint import load_variables
-        load_variables(net.store, ckpt)
-        logger.info('Evaluating %s' % ckpt)
+        load_variables(net.store, ckpt, use_ema=F.use_ema)
+        logger.info('Evaluating %s%s' % (ckpt, ' (averaged weights)' if F.use_ema else ''))
     elif F.synthetic:
         logger.warning('--synthetic: no checkpoint at %r, evaluating randomly initialised weights',
                        F.checkpoint_path)

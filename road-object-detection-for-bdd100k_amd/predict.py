@@ -58,6 +58,9 @@ def parse(argv=None):
                     help='write the first image of every batch with its detections (and ground truth) as PNG '
                          '(the reference shows them with cv2.imshow)')
     ap.add_argument('--output', default=None, help='write detections of the last batch as JSON')
+    ap.add_argument('--use_ema', type=str2bool, default=False,
+                    help='predict with the averaged weights the checkpoint holds (train.py --ema_decay) in place '
+                         'of the variables; an error if it holds none')
     return ap.parse_args(argv)
 
 
@@ -66,7 +69,7 @@ class Predictor(object):
 
     def __init__(self, img_size, device, dtype=torch.float32, checkpoint=None, select_threshold=0.1,
                  nms_threshold=0.4, top_k=400, keep_top_k=200, seed=0, backbone_name='mobilenet_v2',
-                 nms_method='hard', soft_nms_sigma=0.5, soft_nms_min_score=0.001):
+                 nms_method='hard', soft_nms_sigma=0.5, soft_nms_min_score=0.001, use_ema=False):
         from nets.catch_net import CatchNet
         from utils import net_tools
         if nms_method not in ('hard', 'linear', 'gaussian'):
@@ -79,7 +82,7 @@ class Predictor(object):
         self.net = CatchNet(backbone_name, self.config_dict, device, seed)
         if checkpoint is not None:
             from rod.checkpoint import load_variables
-            load_variables(self.net.store, checkpoint)
+            load_variables(self.net.store, checkpoint, use_ema=use_ema)
         self.anchors = net_tools.anchors_all_layer(config.img_size, config.feat_sizes(config.img_size, backbone_name),
                                                    net_tools.init_anchor(6))
         self.dtype = dtype
@@ -183,7 +186,7 @@ def main(argv=None):
         logger.warning('--synthetic: checkpoint %r not found, predicting with random weights', F.checkpoint_all)
     pred = Predictor((F.img_height, F.img_width), dev, dtype, ckpt, F.select_threshold, F.nms_threshold, F.top_k,
                      F.keep_top_k, backbone_name=F.backbone_name, nms_method=F.nms_method,
-                     soft_nms_sigma=F.soft_nms_sigma, soft_nms_min_score=F.soft_nms_min_score)
+                     soft_nms_sigma=F.soft_nms_sigma, soft_nms_min_score=F.soft_nms_min_score, use_ema=F.use_ema)
     logger.info('Building data pileline, using dataset---%s' % 'bdd100k_train')
     source = make_source(F.dataset_dir, F.batch_size, config.img_size, dev, synthetic=F.synthetic, dtype=dtype,
                          num_readers=F.num_readers)

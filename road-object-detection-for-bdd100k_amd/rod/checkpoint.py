@@ -305,50 +305,75 @@ def store_to_tf_layout(name, a):
 
 
 MOMENTUM_SLOT = '/Momentum'   # tf.train.MomentumOptimizer's slot name: <variable>/Momentum
+EMA_SLOT = '/ExponentialMovingAverage'   # tf.train.ExponentialMovingAverage's: <variable>/ExponentialMovingAverage
 
 
-def load_variables(store, path, names_regex=None, optimizer=None):
+def _no_ema(path):
+    return ValueError('checkpoint %r holds no averaged weights (use_ema=True / --use_ema True needs one trained '
+                      'with --ema_decay > 0)' % (path,))
+
+
+def load_variables(store, path, names_regex=None, optimizer=None, use_ema=False):
     """Restore a ParamStore from a torch checkpoint or a TF tensor bundle; returns global_step
     (which drives the optimiser's schedule: the caller sets optimizer.global_step to it).
     names_regex: restore only matching names (the reference's restore_saver filter).
     optimizer: a net_tools.optimizer whose momentum is restored with the variables (zero for a
-    variable the checkpoint holds no momentum of); one without state ignores a stored state."""
+    variable the checkpoint holds no momentum of); one without state ignores a stored state.  One
+    that keeps an EMA has it restored after the variables (a variable the checkpoint holds no
+    average of starts from its restored value).
+    use_ema: every variable (matching names_regex) takes its averaged value in place of its own;
+    buffers (the BatchNorm moving statistics) load as they are.  Raises if the checkpoint holds
+    no average at all."""
     if is_tf_bundle(path):
         tf = read_tf_bundle(path)
         step = int(np.asarray(tf.get('global_step', 0)).reshape(-1)[0]) if 'global_step' in tf else 0
-        sd, mom = {}, {}
+        sd, mom, ema = {}, {}, {}
         for n, t in list(store.params.items()) + list(store.buffers.items()):
             if n in tf:
                 sd[n] = torch.from_numpy(tf_to_store_layout(n, tf[n], t.shape))
             if n + MOMENTUM_SLOT in tf and n in store.params:
                 mom[n] = torch.from_numpy(tf_to_store_layout(n, tf[n + MOMENTUM_SLOT], t.shape))
-        store.load_state_dict(sd, strict=names_regex is None, names_regex=names_regex)
-        if optimizer is not None:
-            optimizer.load_state_dict(mom, names_regex=names_regex)
-        return step
-    if not os.path.isfile(path):
-        raise FileNotFoundError('checkpoint %r not found' % path)
-    sd = torch.load(path, map_location='cpu', weights_only=True)
-    store.load_state_dict(sd['variables'], strict=names_regex is None, names_regex=names_regex)
+            if n + EMA_SLOT in tf and n in store.params:
+                ema[n] = torch.from_numpy(tf_to_store_layout(n, tf[n + EMA_SLOT], t.shape))
+        has_ema = any(k.endswith(EMA_SLOT) for k in tf)
+    else:
+        if not os.path.isfile(path):
+            raise FileNotFoundError('checkpoint %r not found' % path)
+        ck = torch.load(path, map_location='cpu', weights_only=True)
+        sd, mom, ema, step = ck['variables'], ck.get('optimizer', {}), ck.get('ema', {}), int(ck.get('global_step', 0))
+        has_ema = bool(ema)
+    if use_ema:
+        if not has_ema:
+            raise _no_ema(path)
+        sd = dict(sd)
+        sd.update({n: v for n, v in ema.items() if n in store.params})
+    store.load_state_dict(sd, strict=names_regex is None, names_regex=names_regex)
     if optimizer is not None:
-        optimizer.load_state_dict(sd.get('optimizer', {}), names_regex=names_regex)
-    return int(sd.get('global_step', 0))
+        optimizer.load_state_dict(mom, names_regex=names_regex)
+        if getattr(optimizer, 'ema', None) is not None:
+            optimizer.load_ema_state_dict(ema, names_regex=names_regex)
+    return step
 
 
 def save_variables(store, path, step, fmt='torch', optimizer=None):
     """fmt 'torch' (default, what train.py writes) or 'tf' (a tensor bundle at prefix `path`).
     optimizer: a net_tools.optimizer; its momentum (if it keeps one) is saved per variable, as
     the entry 'optimizer' {name: tensor} beside 'variables' (torch) or as slots named
-    <variable>/Momentum in the variable's own TF layout (tf)."""
+    <variable>/Momentum in the variable's own TF layout (tf); its EMA (if it keeps one) as the
+    entry 'ema' {name: tensor} (torch) or as slots named <variable>/ExponentialMovingAverage (tf)."""
     os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
     mom = optimizer.state_dict() if optimizer is not None else {}
+    ema = optimizer.ema_state_dict() if optimizer is not None and hasattr(optimizer, 'ema_state_dict') else {}
     if fmt == 'tf':
         t = {n: store_to_tf_layout(n, v.numpy()) for n, v in store.state_dict().items()}
         t.update({n + MOMENTUM_SLOT: store_to_tf_layout(n, v.numpy()) for n, v in mom.items()})
+        t.update({n + EMA_SLOT: store_to_tf_layout(n, v.numpy()) for n, v in ema.items()})
         t['global_step'] = np.array(step, np.int64)
         write_tf_bundle(path, t)
         return
     ck = {'variables': store.state_dict(), 'global_step': step}
     if mom:
         ck['optimizer'] = mom
+    if ema:
+        ck['ema'] = ema
     torch.save(ck, path)

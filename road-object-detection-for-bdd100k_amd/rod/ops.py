@@ -1272,8 +1272,10 @@ def conv2d_bn(x, w, b, ksize, gamma, beta, mmean, mvar, act, training, decay, ep
 
 def _cinpad_weights(w, cp, dtype):
     """GEMM operand of a [Cout, 3, 3, Cin] weight zero-padded to Cin = cp (inference): cached on the
-    weight, refreshed when the weight changes (its version counter)."""
-    key = (w._version, cp, dtype)
+    weight, refreshed when the weight changes (its version counter, and the owning store's: the
+    update kernels write the flat buffer without touching the tensor's counter)."""
+    st = getattr(w, "_rod_store", None)
+    key = (w._version, st.version if st is not None else None, cp, dtype)
     hit = getattr(w, "_rod_cinpad", None)
     if hit is not None and hit[0] == key:
         return hit[1]
@@ -1599,6 +1601,21 @@ def sgd_momentum_(param_flat: torch.Tensor, grad_flat: torch.Tensor, mom_flat, f
     assert mom_flat is None or (mom_flat.dtype == torch.float32 and mom_flat.numel() == param_flat.numel())
     _abi.call("rod_sgd_momentum", param_flat, grad_flat, mom_flat, flags, param_flat.numel(), lr, scale, float(mu),
               float(wd), float(clip), 1 if nesterov else 0, stream())
+
+
+def sgd_momentum_ema_(param_flat: torch.Tensor, grad_flat: torch.Tensor, mom_flat, ema_flat: torch.Tensor,
+                      flags: torch.Tensor, lr: torch.Tensor, scale, ema_rate: torch.Tensor, mu: float = 0.0,
+                      wd: float = 0.0, clip: float = math.inf, nesterov: bool = False):
+    """rod_sgd_momentum_ema over the flat buffers (formula in include/rod.h): sgd_momentum_ plus, in
+    the same pass, ema_flat -= ema_rate * (ema_flat - param_flat) on the trainable groups.  ema_rate
+    (1 - decay) is a one-element fp32 DEVICE tensor like lr."""
+    assert flags.dtype == torch.uint8 and flags.numel() * 4 == param_flat.numel() == grad_flat.numel()
+    assert lr.dtype == torch.float32 and (scale is None or scale.dtype == torch.float32)
+    assert mom_flat is None or (mom_flat.dtype == torch.float32 and mom_flat.numel() == param_flat.numel())
+    assert ema_flat.dtype == torch.float32 and ema_flat.numel() == param_flat.numel()
+    assert ema_rate.dtype == torch.float32
+    _abi.call("rod_sgd_momentum_ema", param_flat, grad_flat, mom_flat, ema_flat, flags, param_flat.numel(), lr, scale,
+              ema_rate, float(mu), float(wd), float(clip), 1 if nesterov else 0, stream())
 
 
 # ----------------------------------------------------------------------------- deconv pyramid

@@ -217,6 +217,9 @@ def cost(name, a):
     if name == "rod_sgd_momentum":           # read p, g, m and the flags (1 byte / 4 elements), write p, m
         n, mom = a[4], a[2] is not None
         return (20 if mom else 12) * n + n // 4, 9 * n
+    if name == "rod_sgd_momentum_ema":       # read p, g, m, e and the flags, write p, m, e
+        n, mom = a[5], a[2] is not None
+        return (28 if mom else 20) * n + n // 4, 12 * n
     if name == "rod_grad_sqnorm":            # read g and the flags
         n = a[2]
         return 4 * n + n // 4, 2 * n

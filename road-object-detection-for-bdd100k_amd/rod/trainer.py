@@ -17,6 +17,11 @@ With loc_loss='iou' | 'giou' | 'diou' | 'ciou' (opt-in) the ODM box regression i
 boxes instead of the smooth-L1 on the offsets, normalised by the global batch like it (no collective).
 With clf_loss='focal' (opt-in) the classifier loss is the focal loss over every anchor instead,
 normalised by the positives of the global batch (one all-reduce of the counts, ops.focal_lockstep).
+With ema_decay > 0 (opt-in) the optimiser's launch also keeps an exponential moving average of the
+trainable variables (net_tools.optimizer.ema; rod_sgd_momentum_ema).  It adds no collective: every
+rank applies the same reduced gradient to identical parameters, so the ranks' averages are
+identical too.  The step itself is unchanged: in 'full' graph mode the captured step holds the
+fused update, in 'split' and 'eager' modes opt.step() runs it eagerly.
 """
 from __future__ import annotations
 
@@ -39,7 +44,8 @@ class Trainer:
                  sync_bn=False, backbone_name='mobilenet_v2',
                  process_backbone_method=config.process_backbone_method.NONE, momentum=0.0, nesterov=False,
                  weight_decay=0.0, clip_norm=None, warmup_steps=0, fix_learning_rate=True, clf_loss='hnm',
-                 focal_alpha=0.25, focal_gamma=2.0, loc_loss='smooth_l1', loc_loss_weight=1.0):
+                 focal_alpha=0.25, focal_gamma=2.0, loc_loss='smooth_l1', loc_loss_weight=1.0, ema_decay=0.0,
+                 ema_warmup=True):
         self.img_size = tuple(img_size)
         self.batch_size = batch_size          # per-rank batch
         self.world_size = world_size
@@ -65,7 +71,8 @@ class Trainer:
         # new option at its default this is the reference's plain SGD (one rod_sgd_clip launch)
         self.opt = net_tools.optimizer(store, batch_size * world_size, learning_rate,
                                        fix_learning_rate=fix_learning_rate, momentum=momentum, nesterov=nesterov,
-                                       weight_decay=weight_decay, clip_norm=clip_norm, warmup_steps=warmup_steps)
+                                       weight_decay=weight_decay, clip_norm=clip_norm, warmup_steps=warmup_steps,
+                                       ema_decay=ema_decay, ema_warmup=ema_warmup)
         self.reducer = reducer
         if reducer is not None and hasattr(reducer, 'attach'):
             reducer.attach(store)  # buckets over the trainable parameters (rod.ddp)

@@ -22,6 +22,12 @@ Classifier loss (--train_range ALL): by default the reference's (hard-negative m
 Box regression loss of the ODM (--train_range ALL): by default the reference's (masked smooth-L1 on the
 encoded offsets).  --loc_loss iou|giou|diou|ciou replaces it by that loss between the decoded box and
 the matched box, times --loc_loss_weight (default 1.0).
+
+Weight averaging: --ema_decay d (0 < d < 1; default 0 = off) keeps an exponential moving average of
+the trainable variables (tf.train.ExponentialMovingAverage; --ema_warmup True applies its
+num_updates rule min(d, (1 + step) / (10 + step))), updated inside the optimiser's launch, under
+--hip_graph too.  It is saved with every checkpoint and restored on resume; evaluate.py and
+predict.py read it with --use_ema True.
 """
 import argparse
 import json
@@ -112,7 +118,16 @@ def parse(argv=None):
                          'box and the matched box, in its place')
     ap.add_argument('--loc_loss_weight', type=float, default=None,
                     help='weight of the IoU-family box loss in the training loss, finite and >= 0 (default 1.0)')
+    # weight-averaging addition (neutral by default: no average is kept)
+    ap.add_argument('--ema_decay', type=float, default=0.0,
+                    help='keep an exponential moving average of the trainable variables with this decay, in '
+                         '[0, 1) (0 = off); saved with the checkpoints, read by evaluate.py / predict.py --use_ema')
+    ap.add_argument('--ema_warmup', type=str2bool, default=True,
+                    help="the average's decay is min(ema_decay, (1 + step) / (10 + step)) "
+                         '(tf.train.ExponentialMovingAverage with num_updates); False: ema_decay from the first step')
     F = ap.parse_args(argv)
+    if not 0.0 <= F.ema_decay < 1.0:       # (a NaN fails both comparisons)
+        ap.error('--ema_decay must be in [0, 1), got %r' % F.ema_decay)
     loc_given = F.loc_loss_weight is not None
     if F.loc_loss_weight is None:
         F.loc_loss_weight = 1.0
@@ -240,7 +255,10 @@ def main(argv=None):
                       sync_bn=F.sync_bn, momentum=F.momentum, nesterov=F.nesterov, weight_decay=F.weight_decay,
                       clip_norm=F.clip_norm, warmup_steps=F.warmup_steps, fix_learning_rate=F.fix_learning_rate,
                       clf_loss=F.clf_loss, focal_alpha=F.focal_alpha, focal_gamma=F.focal_gamma,
-                      loc_loss=F.loc_loss, loc_loss_weight=F.loc_loss_weight)
+                      loc_loss=F.loc_loss, loc_loss_weight=F.loc_loss_weight, ema_decay=F.ema_decay,
+                      ema_warmup=F.ema_warmup)
+    if F.ema_decay > 0:
+        logger.info('Weight EMA: decay %g%s' % (F.ema_decay, ', num_updates warm-up' if F.ema_warmup else ''))
     if tr_range is config.train_range.ALL:
         logger.info('Classifier loss: %s' % ('focal loss, alpha=%g gamma=%g (no hard-negative mining, no IoU factor)'
                                               % (F.focal_alpha, F.focal_gamma) if F.clf_loss == 'focal'

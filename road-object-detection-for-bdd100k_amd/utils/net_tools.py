@@ -10,6 +10,7 @@ tensors ([B, fh, fw, A, 4] / [B, fh, fw, A, 1]).
 from __future__ import annotations
 
 import collections
+import contextlib
 import math
 
 import numpy as np
@@ -210,10 +211,21 @@ class optimizer(object):
     lives in device memory (`hyper[0]`; `hyper[1]` is the norm-clip scale): a captured step
     reads the value the host last wrote, and the host writes it (refresh(), outside any capture,
     on the step's stream ahead of the step) only when it changes.
+
+    ema_decay > 0 (opt-in; tf.train.ExponentialMovingAverage, which the reference does not use)
+    selects rod_sgd_momentum_ema: the same update, and in the same pass the shadow buffer `ema`
+    (a clone of store.flat made here) follows the parameter just written,
+
+        e = e - (1 - decay) * (e - p)      decay = ema_decay_at(step)
+
+    on the trainable variables.  1 - decay lives in device memory beside the rate (`hyper[2]`)
+    under the same rules.  ema_state_dict / load_ema_state_dict save and restore the average,
+    ema_scope() exchanges it with the variables for an evaluation.
     """
 
     def __init__(self, store, batch_szie, learning_rate=1e-3, fix_learning_rate=True, clip=5.0, momentum=0.0,
-                 nesterov=False, weight_decay=0.0, clip_norm=None, warmup_steps=0, decay=None):
+                 nesterov=False, weight_decay=0.0, clip_norm=None, warmup_steps=0, decay=None, ema_decay=0.0,
+                 ema_warmup=True):
         self.store = store
         self.lr = float(learning_rate)
         self.batch_size = batch_szie
@@ -232,17 +244,30 @@ class optimizer(object):
             raise ValueError('nesterov needs momentum > 0')
         if self.clip_norm is not None and not self.clip_norm > 0:
             raise ValueError('clip_norm must be > 0')
+        self.ema_decay = float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        if not 0.0 <= self.ema_decay < 1.0:      # (NaN fails both comparisons)
+            raise ValueError('ema_decay must satisfy 0 <= ema_decay < 1, got %r' % (ema_decay,))
         self.entry = 'rod_sgd_clip' if (self.momentum == 0 and not self.nesterov and self.weight_decay == 0 and
                                         self.clip_norm is None and self.warmup_steps == 0 and self.fix) \
             else 'rod_sgd_momentum'
-        self.mom = self.flags = self.hyper = self._ws = None
-        self._dev_lr = self._flags_version = None
-        if self.entry == 'rod_sgd_momentum':
+        if self.ema_decay > 0:
+            # with every other option at its default: mu = 0, no momentum buffer, all-trainable or
+            # frozen flags, clip by value: rod_sgd_clip's arithmetic on the trainable variables
+            self.entry = 'rod_sgd_momentum_ema'
+        self.mom = self.flags = self.hyper = self._ws = self.ema = None
+        self._dev_lr = self._dev_ema_rate = self._flags_version = None
+        self._in_ema_scope = False
+        if self.entry != 'rod_sgd_clip':
             dev = store.flat.device
             # momentum 0: m = d is never read back, so no state buffer (same result as m = 0)
             self.mom = torch.zeros_like(store.flat) if self.momentum != 0 else None
             self.flags = torch.zeros(store.numel // 4, dtype=torch.uint8, device=dev)
-            self.hyper = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)   # [lr, scale]
+            if self.ema_decay > 0:
+                self.ema = store.flat.detach().clone()      # alignment padding included
+                self.hyper = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float32, device=dev)   # [lr, scale, 1 - decay]
+            else:
+                self.hyper = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)   # [lr, scale]
             if self.clip_norm is not None and dev.type == 'cuda':
                 self._ws = ops.grad_sqnorm_workspace(dev)
             self.refresh()
@@ -259,6 +284,19 @@ class optimizer(object):
             lr = lr * min(1.0, (step + 1) / self.warmup_steps)
         return lr
 
+    def ema_decay_at(self, step=None):
+        """The decay the update of step `step` (default: the next one) averages with: ema_decay,
+        or with ema_warmup min(ema_decay, (1 + step) / (10 + step)), TF's num_updates rule with
+        num_updates = the number of updates already applied."""
+        step = self.global_step if step is None else step
+        if self.ema_warmup:
+            return min(self.ema_decay, (1.0 + step) / (10.0 + step))
+        return self.ema_decay
+
+    def ema_rate(self, step=None):
+        """1 - ema_decay_at(step) as the fp32 value the device holds (`hyper[2]`)."""
+        return float(np.float32(1.0 - self.ema_decay_at(step)))
+
     def summary_lr(self, step):
         """The `lr` of train.py's summary record: the rate step `step` applied.  The default
         optimiser keeps writing the reference's logged-only decay (quirk 1), as before."""
@@ -271,9 +309,12 @@ class optimizer(object):
         and before every replay."""
         if self.entry == 'rod_sgd_clip':
             return
+        if self._in_ema_scope:      # (step_graphed refreshes ahead of every replay)
+            raise RuntimeError('optimizer.step() inside ema_scope(): the variables hold their averages')
         lr = self.applied_lr()
+        rate = self.ema_rate() if self.ema is not None else None
         stale_flags = self._flags_version != self.store.trainable_version
-        if lr == self._dev_lr and not stale_flags:
+        if lr == self._dev_lr and rate == self._dev_ema_rate and not stale_flags:
             return
         if self.hyper.is_cuda and torch.cuda.is_current_stream_capturing():
             raise RuntimeError('optimizer.refresh() inside a graph capture: the rate or the trainable set '
@@ -284,6 +325,9 @@ class optimizer(object):
         if lr != self._dev_lr:
             self.hyper[:1].fill_(lr)
             self._dev_lr = lr
+        if rate != self._dev_ema_rate:
+            self.hyper[2:3].fill_(rate)
+            self._dev_ema_rate = rate
 
     def state_dict(self):
         """{variable name: momentum} (host copies); empty without a momentum buffer."""
@@ -307,8 +351,61 @@ class optimizer(object):
                 if n in sd:
                     self.mom[o:o + k].copy_(torch.as_tensor(sd[n], dtype=torch.float32).reshape(-1))
 
+    def ema_state_dict(self):
+        """{variable name: averaged value} (host copies); empty without an EMA."""
+        if self.ema is None:
+            return {}
+        return {n: self.ema[o:o + k].view(self.store.params[n].shape).detach().cpu().clone()
+                for n, (o, k) in self.store.offsets.items()}
+
+    def load_ema_state_dict(self, sd, names_regex=None):
+        """Average of every variable (matching names_regex) from `sd`; the variable's current value
+        where `sd` has none (call this after the store was loaded).  Ignored without an EMA."""
+        if self.ema is None:
+            return
+        import re
+        pat = re.compile(names_regex) if names_regex else None
+        with torch.no_grad():
+            for n, (o, k) in self.store.offsets.items():
+                if pat is not None and not pat.match(n):
+                    continue
+                self.ema[o:-(-(o + k) // 4) * 4].zero_()      # the variable and its alignment padding
+                src = torch.as_tensor(sd[n], dtype=torch.float32).reshape(-1) if n in sd \
+                    else self.store.flat[o:o + k].detach()
+                self.ema[o:o + k].copy_(src)
+
+    @contextlib.contextmanager
+    def ema_scope(self):
+        """Within the scope the variables hold their averages (and `ema` the raw values): the
+        contents of store.flat and `ema` are exchanged in place on entry and back on exit, so no
+        data pointer changes and captured step graphs stay valid.  store.version is bumped both
+        times (derived weight layouts follow).  Not legal inside a graph capture; step() raises
+        while the scope is open."""
+        if self.ema is None:
+            raise RuntimeError('ema_scope() needs an optimizer built with ema_decay > 0')
+        if self._in_ema_scope:
+            raise RuntimeError('ema_scope() is already open')
+        self._ema_swap()
+        self._in_ema_scope = True
+        try:
+            yield self
+        finally:
+            self._in_ema_scope = False
+            self._ema_swap()
+
+    def _ema_swap(self):
+        if self.ema.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('optimizer.ema_scope() inside a graph capture')
+        with torch.no_grad():
+            tmp = self.store.flat.detach().clone()
+            self.store.flat.detach().copy_(self.ema)
+            self.ema.copy_(tmp)
+        self.store.version += 1
+
     def step(self):
         st = self.store
+        if self._in_ema_scope:
+            raise RuntimeError('optimizer.step() inside ema_scope(): the variables hold their averages')
         if self.entry == 'rod_sgd_clip':
             ops.sgd_clip_(st.flat, st.flat_grad, self.lr, self.clip)
         else:
@@ -317,8 +414,13 @@ class optimizer(object):
             if self.clip_norm is not None:
                 scale = self.hyper[1:2]
                 ops.grad_sqnorm_(st.flat_grad, self.flags, self.clip_norm, scale, self._ws)
-            ops.sgd_momentum_(st.flat, st.flat_grad, self.mom, self.flags, self.hyper[0:1], scale, self.momentum,
-                              self.weight_decay, float('inf') if self.clip is None else self.clip, self.nesterov)
+            clip = float('inf') if self.clip is None else self.clip
+            if self.ema is not None:
+                ops.sgd_momentum_ema_(st.flat, st.flat_grad, self.mom, self.ema, self.flags, self.hyper[0:1], scale,
+                                      self.hyper[2:3], self.momentum, self.weight_decay, clip, self.nesterov)
+            else:
+                ops.sgd_momentum_(st.flat, st.flat_grad, self.mom, self.flags, self.hyper[0:1], scale, self.momentum,
+                                  self.weight_decay, clip, self.nesterov)
         st.version += 1   # derived weight layouts are refreshed (one batched launch) on next use
         self.global_step += 1
 
