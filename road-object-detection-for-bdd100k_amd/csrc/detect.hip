@@ -11,16 +11,9 @@
 // Compiled with -ffp-contract=off: each expression rounds per op like the TF op chain.
 #include <math.h>
 
-#include "rod_common.h"
+#include "box_common.h"
 
 namespace rod {
-
-constexpr int MAXLV = 8;
-struct Levels {
-  int off[MAXLV + 1];
-  float thr[MAXLV];
-  int L;
-};
 
 // ---------------------------------------------------------------- legacy bilinear
 struct Lerp {
@@ -154,20 +147,8 @@ __global__ void decode_kernel(const float* __restrict__ anc_center, const T* __r
       o[k] = to_f32(oa[i * 4 + k]);
       if (ob) o[k] = o[k] + to_f32(ob[i * 4 + k]);  // refine_out + det_out (predict.py:132)
     }
-    const float cy = o[0] * az[2] + az[0];   // bboxes_cy = off * anchor_h + anchor_cy
-    const float cx = o[1] * az[3] + az[1];
-    const float h = exp_cr(o[2]) * az[2];
-    const float w = exp_cr(o[3]) * az[3];
-    f32x4 r;
-    if (to_corner) {  // centerBboxes_2_cornerBboxes (common_tools.py:30-33)
-      r[0] = cy - h / 2.f;
-      r[1] = cx - w / 2.f;
-      r[2] = cy + h / 2.f;
-      r[3] = cx + w / 2.f;
-    } else {
-      r[0] = cy; r[1] = cx; r[2] = h; r[3] = w;
-    }
-    *(f32x4*)(out + i * 4) = r;
+    const f32x4 z = decode_center(az, o);
+    *(f32x4*)(out + i * 4) = to_corner ? center_to_corner(z) : z;
   }
 }
 
@@ -180,29 +161,16 @@ __global__ void det_targets_kernel(const float* __restrict__ anc_center, const T
                                    float* __restrict__ iou_out, long BA, int A) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < BA; i += (long)gridDim.x * blockDim.x) {
     const int a = (int)(i % A);
-    int l = 0;
-#pragma unroll
-    for (int k = 1; k < MAXLV; ++k)
-      if (k < lv.L && a >= lv.off[k]) l = k;
+    const int l = level_of(lv, a);
     const f32x4 az = *(const f32x4*)(anc_center + (long)a * 4);
     float ro[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) ro[k] = to_f32(refine_out[i * 4 + k]);
     // adjusted anchor = corner(decode(anchor, refine_out))   (net_tools.py:459-460)
-    const float cy = ro[0] * az[2] + az[0], cx = ro[1] * az[3] + az[1];
-    const float h = exp_cr(ro[2]) * az[2], w = exp_cr(ro[3]) * az[3];
-    const float ay0 = cy - h / 2.f, ax0 = cx - w / 2.f, ay1 = cy + h / 2.f, ax1 = cx + w / 2.f;
+    const f32x4 ac = center_to_corner(decode_center(az, ro));
     // gt corner (net_tools.py:463)
-    const f32x4 gz = *(const f32x4*)(cbox + i * 4);
-    const float gy0 = gz[0] - gz[2] / 2.f, gx0 = gz[1] - gz[3] / 2.f;
-    const float gy1 = gz[0] + gz[2] / 2.f, gx1 = gz[1] + gz[3] / 2.f;
-    // jaccard (net_tools.py:254-266)
-    const float vol_a = (ax1 - ax0) * (ay1 - ay0);
-    const float ih = fmaxf(fminf(ay1, gy1) - fmaxf(ay0, gy0), 0.f);
-    const float iw = fmaxf(fminf(ax1, gx1) - fmaxf(ax0, gx0), 0.f);
-    const float inter = ih * iw;
-    const float uni = vol_a - inter + (gy1 - gy0) * (gx1 - gx0);
-    const float iou = inter / uni;
+    const f32x4 gc = center_to_corner(*(const f32x4*)(cbox + i * 4));
+    const float iou = jaccard_ref(ac, vol_anchor(ac), gc, vol_gt(gc));
     const int pos = (iou >= lv.thr[l] ? 1 : 0) * refine_pos[i];  // net_tools.py:468-469
     const float pm = (float)pos;
     const f32x4 rg = *(const f32x4*)(refine_gt + i * 4);
@@ -233,38 +201,18 @@ __global__ void det_targets_bwd_kernel(const float* __restrict__ anc_center, con
     float ro[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) ro[k] = to_f32(refine_out[i * 4 + k]);
-    const float cy = ro[0] * az[2] + az[0], cx = ro[1] * az[3] + az[1];
-    const float h = exp_cr(ro[2]) * az[2], w = exp_cr(ro[3]) * az[3];
-    const float ay0 = cy - h / 2.f, ax0 = cx - w / 2.f, ay1 = cy + h / 2.f, ax1 = cx + w / 2.f;
-    const f32x4 gz = *(const f32x4*)(cbox + i * 4);
-    const float gy0 = gz[0] - gz[2] / 2.f, gx0 = gz[1] - gz[3] / 2.f;
-    const float gy1 = gz[0] + gz[2] / 2.f, gx1 = gz[1] + gz[3] / 2.f;
+    const f32x4 z = decode_center(az, ro);
+    const f32x4 ac = center_to_corner(z);
+    const f32x4 gc = center_to_corner(*(const f32x4*)(cbox + i * 4));
     float g[4] = {0.f, 0.f, 0.f, 0.f};
     const float G = g_iou ? g_iou[i] : 0.f;
     if (G != 0.f) {
-      const float vol_a = (ax1 - ax0) * (ay1 - ay0);
-      const float ihr = fminf(ay1, gy1) - fmaxf(ay0, gy0);
-      const float iwr = fminf(ax1, gx1) - fmaxf(ax0, gx0);
-      const float ih = fmaxf(ihr, 0.f), iw = fmaxf(iwr, 0.f);
-      const float inter = ih * iw;
-      const float uni = vol_a - inter + (gy1 - gy0) * (gx1 - gx0);
-      const float q = G * inter / (uni * uni);
-      const float d_inter = G / uni + q;  // d iou/d inter, with union = vol_a - inter + vol_g
-      const float d_vol = -q;
-      const float d_ih = ihr >= 0.f ? d_inter * iw : 0.f;
-      const float d_iw = iwr >= 0.f ? d_inter * ih : 0.f;
-      float d_ay1 = ay1 <= gy1 ? d_ih : 0.f, d_ay0 = ay0 >= gy0 ? -d_ih : 0.f;
-      float d_ax1 = ax1 <= gx1 ? d_iw : 0.f, d_ax0 = ax0 >= gx0 ? -d_iw : 0.f;
-      d_ax1 += d_vol * (ay1 - ay0);
-      d_ax0 -= d_vol * (ay1 - ay0);
-      d_ay1 += d_vol * (ax1 - ax0);
-      d_ay0 -= d_vol * (ax1 - ax0);
-      const float d_cy = d_ay0 + d_ay1, d_h = (d_ay1 - d_ay0) / 2.f;
-      const float d_cx = d_ax0 + d_ax1, d_w = (d_ax1 - d_ax0) / 2.f;
-      g[0] = d_cy * az[2];
-      g[1] = d_cx * az[3];
-      g[2] = d_h * h;
-      g[3] = d_w * w;
+      const Jaccard j = jaccard_ref_parts(ac, vol_anchor(ac), gc, vol_gt(gc));
+      const float q = G * j.inter / (j.uni * j.uni);
+      const float d_inter = G / j.uni + q;  // d iou/d inter, with union = vol_a - inter + vol_g
+      const f32x4 go = decode_center_bwd(jaccard_ref_bwd<false>(ac, gc, j, d_inter, -q), az, z);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) g[k] = go[k];
     }
     if (g_det_gt) {
       const float pm = (float)det_pos[i];
@@ -280,28 +228,24 @@ __global__ void det_targets_bwd_kernel(const float* __restrict__ anc_center, con
 template <typename T>
 __global__ void softmax_kernel(const T* __restrict__ logits, float* __restrict__ probs, long rows, int K) {
   for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (long)gridDim.x * blockDim.x) {
-    const T* x = logits + r * K;
-    float m = to_f32(x[0]);
-    for (int k = 1; k < K; ++k) m = fmaxf(m, to_f32(x[k]));
-    float e[16];
-    float s = 0.f;
-    for (int k = 0; k < K; ++k) {
-      e[k] = exp_cr(to_f32(x[k]) - m);
-      s += e[k];
-    }
+    float e[16], m, s;
+    row_softmax(logits + r * K, K, e, m, s);
     for (int k = 0; k < K; ++k) probs[r * K + k] = e[k] / s;
   }
 }
 
 static int ew_grid(long n) { return (int)std::min<long>(cdivl(n, 256), 8192); }
 
-static int fill_lv(Levels& lv, const int* off, const float* thr, int L, int A) {
-  ROD_CHECK_ARG(L >= 1 && L <= MAXLV, "levels: L=%d out of range", L);
-  lv.L = L;
-  for (int i = 0; i <= MAXLV; ++i) lv.off[i] = i <= L ? off[i] : A;
-  for (int i = 0; i < MAXLV; ++i) lv.thr[i] = (thr && i < L) ? thr[i] : 0.f;
-  ROD_CHECK_ARG(lv.off[0] == 0 && lv.off[L] == A, "levels: offsets must span [0, A]");
-  return 0;
+// one grid-stride launch of 256-thread blocks over n items
+template <typename... P, typename... A>
+static void ew_launch(void (*kern)(P...), long n, void* stream, A... args) {
+  hipLaunchKernelGGL(kern, dim3(ew_grid(n)), dim3(256), 0, ROD_STREAM(stream), args...);
+}
+// the tail of every entry here: launch(T{}) for the dtype code's storage type T, then the launch check
+template <typename F>
+static int ew_entry(const char* who, int dtype, F&& launch) {
+  ROD_CHECK_ARG(sel_dtype(dtype, launch), "%s: unsupported dtype code %d", who, dtype);
+  return check_launch(who);
 }
 
 }  // namespace rod
@@ -315,9 +259,10 @@ int rod_resize_bilinear(const void* x, void* y, int N, int H, int W, int C, int 
   ROD_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && Ho > 0 && Wo > 0, "rod_resize_bilinear: bad shape");
   const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;  // CalculateResizeScale, no align_corners
   const long n = (long)N * Ho * Wo * C;
-  ROD_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(resize_fwd_kernel<T>, dim3(ew_grid(n)), dim3(256), 0,
-                                               ROD_STREAM(stream), (const T*)x, (T*)y, N, H, W, C, Ho, Wo, sy, sx));
-  return check_launch("rod_resize_bilinear");
+  return ew_entry("rod_resize_bilinear", dtype, [&](auto tt) {
+    typedef decltype(tt) T;
+    ew_launch(resize_fwd_kernel<T>, n, stream, (const T*)x, (T*)y, N, H, W, C, Ho, Wo, sy, sx);
+  });
 }
 
 int rod_resize_bilinear_bwd(const void* dy, void* dx, int N, int H, int W, int C, int Ho, int Wo, int dtype,
@@ -325,9 +270,10 @@ int rod_resize_bilinear_bwd(const void* dy, void* dx, int N, int H, int W, int C
   ROD_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && Ho > 0 && Wo > 0, "rod_resize_bilinear_bwd: bad shape");
   const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
   const long n = (long)N * H * W * C;
-  ROD_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(resize_bwd_kernel<T>, dim3(ew_grid(n)), dim3(256), 0,
-                                               ROD_STREAM(stream), (const T*)dy, (T*)dx, N, H, W, C, Ho, Wo, sy, sx));
-  return check_launch("rod_resize_bilinear_bwd");
+  return ew_entry("rod_resize_bilinear_bwd", dtype, [&](auto tt) {
+    typedef decltype(tt) T;
+    ew_launch(resize_bwd_kernel<T>, n, stream, (const T*)dy, (T*)dx, N, H, W, C, Ho, Wo, sy, sx);
+  });
 }
 
 int rod_depth_to_space2(const void* z, void* out, int N, int h, int w, int F, int Ho, int Wo, int ldo, int dtype,
@@ -336,9 +282,10 @@ int rod_depth_to_space2(const void* z, void* out, int N, int h, int w, int F, in
   ROD_CHECK_ARG(Ho <= 2 * h && Wo <= 2 * w && Ho > 2 * h - 2 && Wo > 2 * w - 2, "rod_depth_to_space2: bad crop");
   if (ldo == 0) ldo = F;
   const long n = (long)N * Ho * Wo * F;
-  ROD_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(d2s_kernel<T>, dim3(ew_grid(n)), dim3(256), 0, ROD_STREAM(stream),
-                                               (const T*)z, (T*)out, N, h, w, F, Ho, Wo, ldo));
-  return check_launch("rod_depth_to_space2");
+  return ew_entry("rod_depth_to_space2", dtype, [&](auto tt) {
+    typedef decltype(tt) T;
+    ew_launch(d2s_kernel<T>, n, stream, (const T*)z, (T*)out, N, h, w, F, Ho, Wo, ldo);
+  });
 }
 
 int rod_space_to_depth2(const void* dout, void* dz, int N, int h, int w, int F, int Ho, int Wo, int ldo, int dtype,
@@ -347,42 +294,44 @@ int rod_space_to_depth2(const void* dout, void* dz, int N, int h, int w, int F, 
   ROD_CHECK_ARG(Ho <= 2 * h && Wo <= 2 * w, "rod_space_to_depth2: bad crop");
   if (ldo == 0) ldo = F;
   const long n = (long)N * h * w * 4 * F;
-  ROD_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(s2d_kernel<T>, dim3(ew_grid(n)), dim3(256), 0, ROD_STREAM(stream),
-                                               (const T*)dout, (T*)dz, N, h, w, F, Ho, Wo, ldo));
-  return check_launch("rod_space_to_depth2");
+  return ew_entry("rod_space_to_depth2", dtype, [&](auto tt) {
+    typedef decltype(tt) T;
+    ew_launch(s2d_kernel<T>, n, stream, (const T*)dout, (T*)dz, N, h, w, F, Ho, Wo, ldo);
+  });
 }
 
 int rod_add(const void* a, const void* b, void* c, long n, int dtype, void* stream) {
   ROD_CHECK_ARG(n >= 0, "rod_add: n < 0");
   if (n == 0) return 0;
-  ROD_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(add_kernel<T>, dim3(ew_grid(n)), dim3(256), 0, ROD_STREAM(stream),
-                                               (const T*)a, (const T*)b, (T*)c, n));
-  return check_launch("rod_add");
+  return ew_entry("rod_add", dtype, [&](auto tt) {
+    typedef decltype(tt) T;
+    ew_launch(add_kernel<T>, n, stream, (const T*)a, (const T*)b, (T*)c, n);
+  });
 }
 
 int rod_decode(const float* anc_center, const void* off_a, const void* off_b, float* out, int B, int A, int to_corner,
                int dtype, void* stream) {
   ROD_CHECK_ARG(B > 0 && A > 0, "rod_decode: bad shape");
   const long BA = (long)B * A;
-  ROD_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(decode_kernel<T>, dim3(ew_grid(BA)), dim3(256), 0,
-                                               ROD_STREAM(stream), anc_center, (const T*)off_a, (const T*)off_b, out,
-                                               BA, A, to_corner));
-  return check_launch("rod_decode");
+  return ew_entry("rod_decode", dtype, [&](auto tt) {
+    typedef decltype(tt) T;
+    ew_launch(decode_kernel<T>, BA, stream, anc_center, (const T*)off_a, (const T*)off_b, out, BA, A, to_corner);
+  });
 }
 
 int rod_det_targets(const float* anc_center, const void* refine_out, const float* refine_gt, const float* cbox,
                     const int* label, const int* refine_pos, const int* lvl_off, const float* thr, int L,
                     float* det_gt, int* det_pos, int* det_lbl, float* iou, int B, int A, int dtype, void* stream) {
   ROD_CHECK_ARG(B > 0 && A > 0, "rod_det_targets: bad shape");
-  ROD_CHECK_ARG(lvl_off && thr, "rod_det_targets: lvl_off/thr host arrays required");
+  ROD_CHECK_ARG(thr, "rod_det_targets: thr is a host array and must be given");
   Levels lv;
-  int e = fill_lv(lv, lvl_off, thr, L, A);
-  if (e) return e;
+  if (int rc = fill_levels(lv, lvl_off, thr, L, A)) return rc;
   const long BA = (long)B * A;
-  ROD_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(det_targets_kernel<T>, dim3(ew_grid(BA)), dim3(256), 0,
-                                               ROD_STREAM(stream), anc_center, (const T*)refine_out, refine_gt, cbox,
-                                               label, refine_pos, lv, det_gt, det_pos, det_lbl, iou, BA, A));
-  return check_launch("rod_det_targets");
+  return ew_entry("rod_det_targets", dtype, [&](auto tt) {
+    typedef decltype(tt) T;
+    ew_launch(det_targets_kernel<T>, BA, stream, anc_center, (const T*)refine_out, refine_gt, cbox, label, refine_pos,
+              lv, det_gt, det_pos, det_lbl, iou, BA, A);
+  });
 }
 
 int rod_det_targets_bwd(const float* anc_center, const void* refine_out, const float* cbox, const int* det_pos,
@@ -390,18 +339,20 @@ int rod_det_targets_bwd(const float* anc_center, const void* refine_out, const f
                         void* stream) {
   ROD_CHECK_ARG(B > 0 && A > 0 && g_refine_out, "rod_det_targets_bwd: bad arguments");
   const long BA = (long)B * A;
-  ROD_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(det_targets_bwd_kernel<T>, dim3(ew_grid(BA)), dim3(256), 0,
-                                               ROD_STREAM(stream), anc_center, (const T*)refine_out, cbox, det_pos,
-                                               g_det_gt, g_iou, (T*)g_refine_out, BA, A));
-  return check_launch("rod_det_targets_bwd");
+  return ew_entry("rod_det_targets_bwd", dtype, [&](auto tt) {
+    typedef decltype(tt) T;
+    ew_launch(det_targets_bwd_kernel<T>, BA, stream, anc_center, (const T*)refine_out, cbox, det_pos, g_det_gt, g_iou,
+              (T*)g_refine_out, BA, A);
+  });
 }
 
 int rod_softmax(const void* logits, float* probs, long rows, int K, int dtype, void* stream) {
   ROD_CHECK_ARG(rows >= 0 && K > 0 && K <= 16, "rod_softmax: bad shape (K <= 16)");
   if (rows == 0) return 0;
-  ROD_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(softmax_kernel<T>, dim3(ew_grid(rows)), dim3(256), 0,
-                                               ROD_STREAM(stream), (const T*)logits, probs, rows, K));
-  return check_launch("rod_softmax");
+  return ew_entry("rod_softmax", dtype, [&](auto tt) {
+    typedef decltype(tt) T;
+    ew_launch(softmax_kernel<T>, rows, stream, (const T*)logits, probs, rows, K);
+  });
 }
 
 }  // extern "C"

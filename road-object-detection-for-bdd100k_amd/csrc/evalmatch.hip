@@ -18,11 +18,11 @@
 //   phase 2  first[g][T] (LDS, INT_MAX): atomicMin(first[idx][t], i) for every t with
 //            nd && match; barrier; tp_it = first[idx][t] == i.  Integer min is
 //            order-independent: the output is deterministic.
-// IoU: oracle.post.bboxes_jaccard_one, one fp32 operation at a time (the build is
-// -ffp-contract=off), the division of nms.hip (IEEE `/`).
+// IoU: jaccard_eval (box_common.h) = oracle.post.bboxes_jaccard_one, one fp32 operation at a time
+// (the build is -ffp-contract=off), the division of nms.hip (IEEE `/`).
 #include <limits.h>
 
-#include "rod_common.h"
+#include "box_common.h"
 
 namespace rod {
 
@@ -80,17 +80,7 @@ __global__ void __launch_bounds__(EM_T) match_detections_kernel(
     float best = -1.f;  // every jac is >= 0: box 0 always takes the first comparison
     int idx = 0;
     for (int j = 0; j < g; ++j) {
-      const f32x4 q = gbox[j];
-      const float h = fmaxf(fminf(q[2], r[2]) - fmaxf(q[0], r[0]), 0.f);
-      const float w = fmaxf(fminf(q[3], r[3]) - fmaxf(q[1], r[1]), 0.f);
-      const float inter = h * w;
-      float jac = 0.f;
-      // inter == 0 or another label gives exactly 0 (0 / union, iou * 0.0f): skip the division
-      if (inter > 0.f && glab[j] == label) {
-        const float area_g = (q[2] - q[0]) * (q[3] - q[1]);
-        const float uni = (-inter + area_g) + area_det;
-        jac = uni > 0.f ? inter / uni : 0.f;
-      }
+      const float jac = jaccard_eval(gbox[j], r, area_det, glab[j] == label);
       if (jac > best) {  // strict: the first maximum wins
         best = jac;
         idx = j;

@@ -14,16 +14,11 @@
 // pass, without the selection and without the IoU factor; semantics in include/rod.h.
 #include <math.h>
 
-#include "rod_common.h"
+#include "box_common.h"
 
 namespace rod {
 
-constexpr int HNM_MAXL = 8;
 constexpr int HNM_K = 16;  // max classes
-struct HnmLevels {
-  int off[HNM_MAXL + 1];
-  int L;
-};
 
 // state words (int): [0] k  [1] prefix bits  [2] remaining rank  [3] n_pos  [4] n_neg  [5] n_neg_sel
 // float outputs (8): pos_loss, neg_loss, clf_loss, max_hard_pred, n_pos, k, n_neg_selected, 0
@@ -35,17 +30,6 @@ struct HnmWs {
   int* cnt_slab;     // [nb][2]
   double* loss_slab; // [nb][3]
 };
-
-template <typename T>
-__device__ __forceinline__ void row_softmax(const T* __restrict__ x, int K, float* e, float& m, float& s) {
-  m = to_f32(x[0]);
-  for (int k = 1; k < K; ++k) m = fmaxf(m, to_f32(x[k]));
-  s = 0.f;
-  for (int k = 0; k < K; ++k) {
-    e[k] = exp_cr(to_f32(x[k]) - m);
-    s += e[k];
-  }
-}
 
 template <typename T>
 __global__ void __launch_bounds__(256) hnm_rows_kernel(const T* __restrict__ logits, const int* __restrict__ pos,
@@ -145,7 +129,7 @@ __global__ void radix_scan_kernel(int shift, int* __restrict__ state, unsigned* 
 }
 
 // per (image, level) group: mean, sd = sqrt(var + 1e-8), zmin, den = max(z') + 1e-8
-__global__ void __launch_bounds__(256) iou_group_kernel(const float* __restrict__ iou, HnmLevels lv, int A,
+__global__ void __launch_bounds__(256) iou_group_kernel(const float* __restrict__ iou, Levels lv, int A,
                                                         float* __restrict__ gstat) {
   __shared__ double sd[256];
   __shared__ float smin[256], smax[256];
@@ -210,7 +194,7 @@ template <typename T>
 __global__ void __launch_bounds__(256) hnm_loss_kernel(const T* __restrict__ logits, const int* __restrict__ lbl,
                                                        const int* __restrict__ pos, const float* __restrict__ iou,
                                                        const float* __restrict__ nval, const float* __restrict__ gstat,
-                                                       const int* __restrict__ state, HnmLevels lv, long R, int A,
+                                                       const int* __restrict__ state, Levels lv, long R, int A,
                                                        int K, float inv_bs, T* __restrict__ grad,
                                                        double* __restrict__ slab) {
   __shared__ double red[3][4];
@@ -224,10 +208,7 @@ __global__ void __launch_bounds__(256) hnm_loss_kernel(const T* __restrict__ log
     const bool ng = !p && nval[r] < thr;  // logical_and(nmask, nvalues < max_hard_pred)
     const int a = (int)(r % A);
     const int b = (int)(r / A);
-    int l = 0;
-#pragma unroll
-    for (int q = 1; q < HNM_MAXL; ++q)
-      if (q < lv.L && a >= lv.off[q]) l = q;
+    const int l = level_of(lv, a);
     const float lse = log_cr(s);
     const int lab = lbl[r];
     float wp = 0.f, wn = 0.f;
@@ -352,7 +333,7 @@ __global__ void hnm_begin_kernel(const int* __restrict__ counts, int B, int* __r
 template <typename T>
 __global__ void __launch_bounds__(256) iou_factor_bwd_kernel(const T* __restrict__ logits, const int* __restrict__ lbl,
                                                              const int* __restrict__ pos, const float* __restrict__ iou,
-                                                             HnmLevels lv, int A, int K, float inv_bs,
+                                                             Levels lv, int A, int K, float inv_bs,
                                                              float* __restrict__ g_iou) {
   __shared__ double sd[4][256];
   __shared__ float smin[256], smax[256];
@@ -420,10 +401,8 @@ __global__ void __launch_bounds__(256) iou_factor_bwd_kernel(const T* __restrict
     float a = 0.f;
     if (pos[r] != 0) {
       const T* x = logits + r * K;
-      float m = to_f32(x[0]);
-      for (int k = 1; k < K; ++k) m = fmaxf(m, to_f32(x[k]));
-      float se = 0.f;
-      for (int k = 0; k < K; ++k) se += exp_cr(to_f32(x[k]) - m);
+      float e[HNM_K], m, se;
+      row_softmax(x, K, e, m, se);
       const float ce = log_cr(se) - (to_f32(x[lbl[r]]) - m);
       a = ce * inv_bs * (4.f * powf(w, 3.f));
     }
@@ -747,18 +726,16 @@ int rod_softmax_ce_hnm(const void* logits, const int* det_lbl, const int* det_po
                        const int* lvl_off, int L, float bs, float* out, void* grad, void* workspace, int B, int A,
                        int K, int dtype, void* stream) {
   ROD_CHECK_ARG(B > 0 && A > 0 && K > 1 && K <= HNM_K, "rod_softmax_ce_hnm: bad shape (K <= 16)");
-  ROD_CHECK_ARG(L >= 1 && L <= HNM_MAXL && lvl_off, "rod_softmax_ce_hnm: bad levels");
-  ROD_CHECK_ARG(lvl_off[0] == 0 && lvl_off[L] == A, "rod_softmax_ce_hnm: level offsets must span [0, A]");
+  Levels lv;
+  if (int rc = fill_levels(lv, lvl_off, nullptr, L, A)) return rc;
   ROD_CHECK_ARG(workspace && out, "rod_softmax_ce_hnm: workspace/out NULL");
-  HnmLevels lv;
-  lv.L = L;
-  for (int i = 0; i <= HNM_MAXL; ++i) lv.off[i] = i <= L ? lvl_off[i] : A;
   const long R = (long)B * A;
   const int nb = hnm_blocks(R);
   HnmWs w = carve(workspace, R, B, L, nb);
   hipStream_t s = ROD_STREAM(stream);
   const float inv_bs = 1.0f / bs;
-  ROD_DISPATCH_DTYPE(dtype, {
+  auto run = [&](auto tt) {
+    typedef decltype(tt) T;
     hipLaunchKernelGGL(hnm_rows_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)logits, det_pos, R, K, w.nval,
                        w.cnt_slab);
     hipLaunchKernelGGL(hnm_count_kernel, dim3(1), dim3(256), 0, s, w.cnt_slab, nb, B, w.state, w.hist);
@@ -770,7 +747,8 @@ int rod_softmax_ce_hnm(const void* logits, const int* det_lbl, const int* det_po
     hipLaunchKernelGGL(hnm_loss_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)logits, det_lbl, det_pos, iou, w.nval,
                        w.gstat, w.state, lv, R, A, K, inv_bs, (T*)grad, w.loss_slab);
     hipLaunchKernelGGL(hnm_finalize_kernel, dim3(1), dim3(256), 0, s, w.loss_slab, nb, w.state, bs, out);
-  });
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_softmax_ce_hnm: unsupported dtype code %d", dtype);
   return check_launch("rod_softmax_ce_hnm");
 }
 
@@ -778,14 +756,14 @@ int rod_iou_factor_bwd(const void* logits, const int* det_lbl, const int* det_po
                        const int* lvl_off, int L, float bs, float* g_iou, int B, int A, int K, int dtype,
                        void* stream) {
   ROD_CHECK_ARG(B > 0 && A > 0 && K > 1 && K <= HNM_K && g_iou, "rod_iou_factor_bwd: bad arguments");
-  ROD_CHECK_ARG(L >= 1 && L <= HNM_MAXL && lvl_off && lvl_off[0] == 0 && lvl_off[L] == A,
-                "rod_iou_factor_bwd: bad levels");
-  HnmLevels lv;
-  lv.L = L;
-  for (int i = 0; i <= HNM_MAXL; ++i) lv.off[i] = i <= L ? lvl_off[i] : A;
-  ROD_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(iou_factor_bwd_kernel<T>, dim3(B * L), dim3(256), 0,
-                                               ROD_STREAM(stream), (const T*)logits, det_lbl, det_pos, iou, lv, A, K,
-                                               1.0f / bs, g_iou));
+  Levels lv;
+  if (int rc = fill_levels(lv, lvl_off, nullptr, L, A)) return rc;
+  auto run = [&](auto tt) {
+    typedef decltype(tt) T;
+    hipLaunchKernelGGL(iou_factor_bwd_kernel<T>, dim3(B * L), dim3(256), 0, ROD_STREAM(stream), (const T*)logits,
+                       det_lbl, det_pos, iou, lv, A, K, 1.0f / bs, g_iou);
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_iou_factor_bwd: unsupported dtype code %d", dtype);
   return check_launch("rod_iou_factor_bwd");
 }
 
@@ -799,8 +777,12 @@ int rod_hnm_rows(const void* logits, const int* det_pos, void* workspace, int* c
   const int nb = hnm_blocks(R);
   HnmWs w = carve(workspace, R, B, L, nb);
   hipStream_t s = ROD_STREAM(stream);
-  ROD_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(hnm_rows_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)logits,
-                                               det_pos, R, K, w.nval, w.cnt_slab));
+  auto run = [&](auto tt) {
+    typedef decltype(tt) T;
+    hipLaunchKernelGGL(hnm_rows_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)logits, det_pos, R, K, w.nval,
+                       w.cnt_slab);
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_hnm_rows: unsupported dtype code %d", dtype);
   hipLaunchKernelGGL(hnm_sum_counts_kernel, dim3(1), dim3(256), 0, s, w.cnt_slab, nb, counts);
   return check_launch("rod_hnm_rows");
 }
@@ -832,22 +814,21 @@ int rod_hnm_loss(const void* logits, const int* det_lbl, const int* det_pos, con
                  int L, float bs, const int* state, float* out, void* grad, void* workspace, int B, int A, int K,
                  int dtype, void* stream) {
   ROD_CHECK_ARG(B > 0 && A > 0 && K > 1 && K <= HNM_K, "rod_hnm_loss: bad shape (K <= 16)");
-  ROD_CHECK_ARG(L >= 1 && L <= HNM_MAXL && lvl_off, "rod_hnm_loss: bad levels");
-  ROD_CHECK_ARG(lvl_off[0] == 0 && lvl_off[L] == A, "rod_hnm_loss: level offsets must span [0, A]");
+  Levels lv;
+  if (int rc = fill_levels(lv, lvl_off, nullptr, L, A)) return rc;
   ROD_CHECK_ARG(workspace && out && state, "rod_hnm_loss: workspace/out/state NULL");
-  HnmLevels lv;
-  lv.L = L;
-  for (int i = 0; i <= HNM_MAXL; ++i) lv.off[i] = i <= L ? lvl_off[i] : A;
   const long R = (long)B * A;
   const int nb = hnm_blocks(R);
   HnmWs w = carve(workspace, R, B, L, nb);
   hipStream_t s = ROD_STREAM(stream);
-  ROD_DISPATCH_DTYPE(dtype, {
+  auto run = [&](auto tt) {
+    typedef decltype(tt) T;
     hipLaunchKernelGGL(iou_group_kernel, dim3(B * L), dim3(256), 0, s, iou, lv, A, w.gstat);
     hipLaunchKernelGGL(hnm_loss_kernel<T>, dim3(nb), dim3(256), 0, s, (const T*)logits, det_lbl, det_pos, iou, w.nval,
                        w.gstat, state, lv, R, A, K, 1.0f / bs, (T*)grad, w.loss_slab);
     hipLaunchKernelGGL(hnm_finalize_kernel, dim3(1), dim3(256), 0, s, w.loss_slab, nb, state, bs, out);
-  });
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_hnm_loss: unsupported dtype code %d", dtype);
   return check_launch("rod_hnm_loss");
 }
 

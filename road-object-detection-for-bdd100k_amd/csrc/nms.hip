@@ -8,24 +8,27 @@
 //            min/max-normalised corners, 0 if either area <= 0 (bboxes.py:182)
 //   pad      zero-pad the kept scores/boxes to keep_top_k (tensors.py:59-86)
 //
-// Two implementations with identical output:
-//  * compacted (select_threshold > 0, workspace given — the CLIs' 0.1 / 0.3): ONE row-wise,
-//    coalesced pass over probs appends every selected (nonzero) score of every class as a
-//    64-bit key (~score bits, anchor index) to a per-(image, class) list
-//    (nms_compact_kernel); then one workgroup per (image, class) sorts its list in LDS (or,
-//    past 4096 candidates, radix-selects the top_k-th key over the list first) and runs the
-//    greedy NMS (nms_select_kernel).  The entries top_k would take beyond the selected ones
-//    have score 0 and a zeroed box (p < threshold): zero area, they suppress nothing and are
-//    output as the zero padding — so they need not be materialised.
-//  * direct (any threshold): per (image, class) an exact in-workgroup 4 x 8-bit radix select
+// Each kernel is front end -> gather -> greedy -> emit.  A front end leaves the m <= top_k
+// candidates of its (image, class) in key[0..m) as 64-bit keys (~score bits, anchor index) sorted
+// ascending by lds_bitonic, which is score descending, index ascending; the back end is shared:
+//   nms_gather        key -> sc[] / bx[] by position, boxes masked like the reference
+//   hard_nms_greedy   or soft_nms_greedy (rod_select_topk_softnms; the kernels are templates on SOFT)
+//   nms_emit          the kept entries and the zero padding
+// The two front ends give identical keys:
+//  * candidate list (nms_compact_kernel + nms_select_kernel; select_threshold > 0 and a workspace
+//    given — the CLIs' 0.1 / 0.3): ONE row-wise, coalesced pass over probs appends every selected
+//    (nonzero) score of every class to a per-(image, class) list; then one workgroup per (image,
+//    class) sorts its list in LDS or, past NMS_SORT candidates, radix-selects the top_k-th key
+//    over the list first.  The entries top_k would take beyond the selected ones have score 0
+//    and a zeroed box (p < threshold): zero area, they suppress nothing and are output as the
+//    zero padding — so they need not be materialised.
+//  * direct (select_topk_nms_kernel; any threshold): an exact in-workgroup 4 x 8-bit radix select
 //    on the (non-negative) f32 score bits read column-wise from probs; candidates compacted in
-//    index order (ties resolved by index), then bitonic-sorted by (score desc, index asc).
-// rod_select_topk_softnms runs the same two front ends (the kernels are templates) and replaces
-// only the greedy stage, by soft_nms_greedy below.
+//    index order (ties resolved by index), then sorted.
 // Compiled with -ffp-contract=off.
 #include <math.h>
 
-#include "rod_common.h"
+#include "box_common.h"
 
 namespace rod {
 
@@ -73,23 +76,68 @@ __device__ unsigned block_radix_kth_largest(const float* probs, long base, int A
   return prefix;  // bits of the k-th largest score
 }
 
-__device__ __forceinline__ float tf_iou(const float* bi, const float* bj) {
-  const float ymin_i = fminf(bi[0], bi[2]), xmin_i = fminf(bi[1], bi[3]);
-  const float ymax_i = fmaxf(bi[0], bi[2]), xmax_i = fmaxf(bi[1], bi[3]);
-  const float ymin_j = fminf(bj[0], bj[2]), xmin_j = fminf(bj[1], bj[3]);
-  const float ymax_j = fmaxf(bj[0], bj[2]), xmax_j = fmaxf(bj[1], bj[3]);
-  const float area_i = (ymax_i - ymin_i) * (xmax_i - xmin_i);
-  const float area_j = (ymax_j - ymin_j) * (xmax_j - xmin_j);
-  if (area_i <= 0.f || area_j <= 0.f) return 0.f;
-  const float iy0 = fmaxf(ymin_i, ymin_j), ix0 = fmaxf(xmin_i, xmin_j);
-  const float iy1 = fminf(ymax_i, ymax_j), ix1 = fminf(xmax_i, xmax_j);
-  const float inter = fmaxf(iy1 - iy0, 0.f) * fmaxf(ix1 - ix0, 0.f);
-  return inter / (area_i + area_j - inter);
+// ------------------------------------------------------------------- the shared back end
+constexpr int NMS_SORT = 4096;   // candidate lists up to this size are sorted whole in LDS
+
+// bitonic sort (ascending) of key[0..P), P a power of two <= NMS_SORT, 1024 threads
+__device__ void lds_bitonic(unsigned long long* key, int P) {
+  for (int size = 2; size <= P; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = threadIdx.x; i < P; i += NMS_T) {
+        const int j = i ^ stride;
+        if (j > i) {
+          const bool up = (i & size) == 0;
+          const unsigned long long ki = key[i], kj = key[j];
+          if ((ki > kj) == up) {
+            key[i] = kj;
+            key[j] = ki;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
 }
 
-// ------------------------------------------------------------------- Soft-NMS greedy stage
-// (rod_select_topk_softnms; semantics in include/rod.h).  Replaces the greedy loop of both
-// kernels below when they are instantiated with SOFT: thread `tid` owns candidate position
+// candidate tid < m is anchor (key[tid] & 0xFFFFFFFF): its score and box (both masked like the
+// reference, net_tools.py:689-692) to sc[tid] / bx[tid]; ends with a barrier
+__device__ __forceinline__ void nms_gather(const unsigned long long* key, int m, const float* __restrict__ probs,
+                                           const float* __restrict__ boxes, long base, int K, int c, float sel_thr,
+                                           float* sc, float (*bx)[4], unsigned char* dead) {
+  const int tid = threadIdx.x;
+  if (tid < m) {
+    const int a = (int)(key[tid] & 0xFFFFFFFFu);
+    const float p = probs[(base + a) * K + c];
+    const float fm = p >= sel_thr ? 1.f : 0.f;
+    sc[tid] = p * fm;
+    const float* bp = boxes + (base + a) * 4;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) bx[tid][q] = bp[q] * fm;
+    dead[tid] = 0;
+  }
+  __syncthreads();
+}
+
+// Hard greedy stage: in sorted order, a live candidate is kept and kills every later one whose
+// tf_iou with it is > nms_thr.  kept_idx[j] is the position of the j-th kept candidate, j < the
+// returned count; the exits are workgroup-uniform and a barrier has made kept_idx visible.
+__device__ __forceinline__ int hard_nms_greedy(int m, int keep_k, float nms_thr, const float (*bx)[4],
+                                               unsigned char* dead, int* kept_idx) {
+  const int tid = threadIdx.x;
+  int kept = 0;
+  for (int i = 0; i < m && kept < keep_k; ++i) {
+    if (dead[i]) continue;  // uniform: dead[] only changes between barriers
+    if (tid == 0) kept_idx[kept] = i;
+    ++kept;
+    for (int j = i + 1 + tid; j < m; j += NMS_T)
+      if (!dead[j] && tf_iou(bx[i], bx[j]) > nms_thr) dead[j] = 1;
+    __syncthreads();
+  }
+  __syncthreads();
+  return kept;
+}
+
+// Soft-NMS greedy stage (rod_select_topk_softnms; semantics in include/rod.h): thread `tid` owns candidate position
 // `tid` (m <= NMS_T) and keeps its working score w in a register; its box stays in bx[tid],
 // which the loop never writes, so the picked box is a broadcast LDS read.  Each iteration is
 // one argmax over the 64-bit key (bits of w) << 32 | (NMS_T - 1 - position): w >= 0, so the
@@ -158,6 +206,20 @@ __device__ __forceinline__ int soft_nms_greedy(int m, int keep_k, float nms_thr,
   }
   __syncthreads();
   return kept;
+}
+
+// the kept entries, then zero padding to keep_k (tensors.py:59-86); the hard stage's scores are
+// still by position, the soft stage left the rescored ones by output slot
+template <bool SOFT>
+__device__ __forceinline__ void nms_emit(int kept, int keep_k, const float* sc, const float (*bx)[4],
+                                         const int* kept_idx, float* __restrict__ os, float* __restrict__ ob) {
+  for (int j = threadIdx.x; j < keep_k; j += NMS_T) {
+    const bool kk = j < kept;
+    const int i = kk ? kept_idx[j] : 0;
+    os[j] = kk ? sc[SOFT ? j : i] : 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) ob[j * 4 + q] = kk ? bx[i][q] : 0.f;
+  }
 }
 
 template <bool SOFT>
@@ -234,73 +296,20 @@ __global__ void __launch_bounds__(NMS_T) select_topk_nms_kernel(const float* __r
     __syncthreads();
   }
   const int n = min(n_out, k);
-  // 3) bitonic sort of n keys (pad to NMS_T)
-  for (int i = tid; i < NMS_T; i += NMS_T)
-    if (i >= n) key[i] = ~0ull;
+  // 3) sort the n keys (padded to NMS_T)
+  if (tid >= n) key[tid] = ~0ull;
   __syncthreads();
-  for (int size = 2; size <= NMS_T; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      const int i = tid;
-      const int j = i ^ stride;
-      if (j > i) {
-        const bool up = (i & size) == 0;
-        const unsigned long long ki = key[i], kj = key[j];
-        if ((ki > kj) == up) {
-          key[i] = kj;
-          key[j] = ki;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  // 4) gather candidate boxes (masked like the reference) and scores
-  if (tid < n) {
-    const int a = (int)(key[tid] & 0xFFFFFFFFu);
-    const float p = probs[(base + a) * K + c];
-    const float fm = p >= sel_thr ? 1.f : 0.f;
-    sc[tid] = p * fm;
-    const float* bp = boxes + (base + a) * 4;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) bx[tid][q] = bp[q] * fm;
-    dead[tid] = 0;
-  }
-  __syncthreads();
-  // 5) greedy NMS in sorted order (SOFT: rescoring loop; hist is free by now)
-  int kept = 0;
-  if constexpr (SOFT) {
-    kept = soft_nms_greedy(n, keep_k, nms_thr, sa, bx, sc, kept_idx, hist);
-  } else {
-    for (int i = 0; i < n && kept < keep_k; ++i) {
-      if (dead[i]) continue;  // uniform: dead[] only changes between barriers
-      if (tid == 0) kept_idx[kept] = i;
-      ++kept;
-      for (int j = i + 1 + tid; j < n; j += NMS_T)
-        if (!dead[j] && tf_iou(bx[i], bx[j]) > nms_thr) dead[j] = 1;
-      __syncthreads();
-    }
-    __syncthreads();
-  }
-  // 6) write kept entries and zero padding
-  float* os = out_scores + ((long)b * (K - 1) + (c - 1)) * keep_k;
-  float* ob = out_boxes + ((long)b * (K - 1) + (c - 1)) * keep_k * 4;
-  for (int j = tid; j < keep_k; j += NMS_T) {
-    if (j < kept) {
-      const int i = kept_idx[j];
-      os[j] = SOFT ? sc[j] : sc[i];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) ob[j * 4 + q] = bx[i][q];
-    } else {
-      os[j] = 0.f;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) ob[j * 4 + q] = 0.f;
-    }
-  }
+  lds_bitonic(key, NMS_T);
+  // 4-6) the shared back end (hist is free by now: the soft stage's scratch)
+  nms_gather(key, n, probs, boxes, base, K, c, sel_thr, sc, bx, dead);
+  const int kept = SOFT ? soft_nms_greedy(n, keep_k, nms_thr, sa, bx, sc, kept_idx, hist)
+                        : hard_nms_greedy(n, keep_k, nms_thr, bx, dead, kept_idx);
+  nms_emit<SOFT>(kept, keep_k, sc, bx, kept_idx, out_scores + ((long)b * (K - 1) + (c - 1)) * keep_k,
+                 out_boxes + ((long)b * (K - 1) + (c - 1)) * keep_k * 4);
 }
-
 
 // ----------------------------------------------------------------- compacted implementation
 constexpr int NMS_CT = 2048;     // anchors per compaction workgroup (8 per thread)
-constexpr int NMS_SORT = 4096;   // candidate lists up to this size are sorted whole in LDS
 constexpr int NMS_MAXC = 32;     // classes per launch (K - 1)
 
 __global__ void nms_zero_kernel(unsigned* p, int n) {
@@ -348,26 +357,6 @@ __global__ void __launch_bounds__(256) nms_compact_kernel(const float* __restric
       if (cand)
         keys[((long)b * C + (c - 1)) * A + lbase[c - 1] + off + __popcll(m & lower)] =
             ((unsigned long long)(~bits) << 32) | (unsigned)a;
-    }
-  }
-}
-
-// bitonic sort (ascending) of key[0..P), P a power of two <= NMS_SORT, 1024 threads
-__device__ void lds_bitonic(unsigned long long* key, int P) {
-  for (int size = 2; size <= P; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int i = threadIdx.x; i < P; i += NMS_T) {
-        const int j = i ^ stride;
-        if (j > i) {
-          const bool up = (i & size) == 0;
-          const unsigned long long ki = key[i], kj = key[j];
-          if ((ki > kj) == up) {
-            key[i] = kj;
-            key[j] = ki;
-          }
-        }
-      }
-      __syncthreads();
     }
   }
 }
@@ -445,41 +434,12 @@ __global__ void __launch_bounds__(NMS_T) nms_select_kernel(const float* __restri
     lds_bitonic(key, P);
     m = k;
   }
-  // gather the m candidates (score desc, index asc), boxes masked as the reference
-  if (tid < m) {
-    const int a = (int)(key[tid] & 0xFFFFFFFFu);
-    const float p = probs[(base + a) * K + c];
-    const float fm = p >= sel_thr ? 1.f : 0.f;
-    sc[tid] = p * fm;
-    const float* bp = boxes + (base + a) * 4;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) bx[tid][q] = bp[q] * fm;
-    dead[tid] = 0;
-  }
-  __syncthreads();
-  int kept = 0;
-  if constexpr (SOFT) {  // hist is free by now
-    kept = soft_nms_greedy(m, keep_k, nms_thr, sa, bx, sc, kept_idx, hist);
-  } else {
-    for (int i = 0; i < m && kept < keep_k; ++i) {
-      if (dead[i]) continue;  // uniform: dead[] only changes between barriers
-      if (tid == 0) kept_idx[kept] = i;
-      ++kept;
-      for (int j = i + 1 + tid; j < m; j += NMS_T)
-        if (!dead[j] && tf_iou(bx[i], bx[j]) > nms_thr) dead[j] = 1;
-      __syncthreads();
-    }
-    __syncthreads();
-  }
-  float* os = out_scores + ((long)b * C + (c - 1)) * keep_k;
-  float* ob = out_boxes + ((long)b * C + (c - 1)) * keep_k * 4;
-  for (int j = tid; j < keep_k; j += NMS_T) {
-    const bool kk = j < kept;
-    const int i = kk ? kept_idx[j] : 0;
-    os[j] = kk ? sc[SOFT ? j : i] : 0.f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) ob[j * 4 + q] = kk ? bx[i][q] : 0.f;
-  }
+  // the shared back end (hist is free by now: the soft stage's scratch)
+  nms_gather(key, m, probs, boxes, base, K, c, sel_thr, sc, bx, dead);
+  const int kept = SOFT ? soft_nms_greedy(m, keep_k, nms_thr, sa, bx, sc, kept_idx, hist)
+                        : hard_nms_greedy(m, keep_k, nms_thr, bx, dead, kept_idx);
+  nms_emit<SOFT>(kept, keep_k, sc, bx, kept_idx, out_scores + ((long)b * C + (c - 1)) * keep_k,
+                 out_boxes + ((long)b * C + (c - 1)) * keep_k * 4);
 }
 
 static size_t nms_counts_bytes(int B, int K) { return ((size_t)B * (K - 1) * sizeof(unsigned) + 255) / 256 * 256; }

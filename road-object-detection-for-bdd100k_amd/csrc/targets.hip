@@ -7,16 +7,9 @@
 // and the oracle uses the same definition.
 #include <math.h>
 
-#include "rod_common.h"
+#include "box_common.h"
 
 namespace rod {
-
-constexpr int MAXL = 8;
-struct LevelInfo {
-  int off[MAXL + 1];
-  float thr[MAXL];
-  int L;
-};
 
 // One workgroup per (anchor block, image).  The image's centre-form GT boxes are staged
 // in LDS together with their corner form and area.
@@ -25,7 +18,7 @@ struct LevelInfo {
 // sum(encode(anchor, box)^2) (tf.argmin, first minimum), every anchor positive.
 template <bool NN>
 __global__ void __launch_bounds__(256) match_anchors_kernel(const float* __restrict__ anc_corner,
-                                                            const float* __restrict__ anc_center, LevelInfo li,
+                                                            const float* __restrict__ anc_center, Levels li,
                                                             const float* __restrict__ gt, const int* __restrict__ gt_lbl,
                                                             const int* __restrict__ gt_n, float* __restrict__ out_off,
                                                             float* __restrict__ out_cbox, int* __restrict__ out_lbl,
@@ -46,11 +39,10 @@ __global__ void __launch_bounds__(256) match_anchors_kernel(const float* __restr
     // center_bboxes[i] = (cy, cx, h, w) (train.py:109 already converted them)
     const float* p = gt + ((long)b * G + g) * 4;
     const float cy = p[0], cx = p[1], h = p[2], w = p[3];
-    // centerBboxes_2_cornerBboxes (common_tools.py:30-33), used by jaccard (net_tools.py:323, 398)
-    const float y0 = cy - h / 2.f, x0 = cx - w / 2.f, y1 = cy + h / 2.f, x1 = cx + w / 2.f;
-    gc[g * 4 + 0] = y0; gc[g * 4 + 1] = x0; gc[g * 4 + 2] = y1; gc[g * 4 + 3] = x1;
+    const f32x4 c = center_to_corner(p);  // the corner form jaccard takes (net_tools.py:323, 398)
+    gc[g * 4 + 0] = c[0]; gc[g * 4 + 1] = c[1]; gc[g * 4 + 2] = c[2]; gc[g * 4 + 3] = c[3];
     gz[g * 4 + 0] = cy; gz[g * 4 + 1] = cx; gz[g * 4 + 2] = h; gz[g * 4 + 3] = w;
-    gv[g] = (y1 - y0) * (x1 - x0);  // jaccard: (ymax-ymin)*(xmax-xmin) of the gt (net_tools.py:265)
+    gv[g] = vol_gt(c);
     gl[g] = gt_lbl[(long)b * G + g];
     // every box contributes mask*encode(box) to every anchor (net_tools.py:340-342): a
     // non-finite encoding turns 0*x into NaN for all anchors (kept for parity).
@@ -67,14 +59,10 @@ __global__ void __launch_bounds__(256) match_anchors_kernel(const float* __restr
 
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   if (a >= A) return;
-  int lvl = 0;
-#pragma unroll
-  for (int l = 1; l < MAXL; ++l)
-    if (l < li.L && a >= li.off[l]) lvl = l;
+  const int lvl = level_of(li, a);
 
   const f32x4 ac = *(const f32x4*)(anc_corner + (long)a * 4);
-  const float aymin = ac[0], axmin = ac[1], aymax = ac[2], axmax = ac[3];
-  const float vol_a = (axmax - axmin) * (aymax - aymin);  // net_tools.py:254
+  const float vol_a = vol_anchor(ac);
 
   float best = 0.f;
   int idx = 0;
@@ -91,21 +79,13 @@ __global__ void __launch_bounds__(256) match_anchors_kernel(const float* __restr
       }
     }
   } else {
-  for (int g = 0; g < n; ++g) {
-    const float iy0 = fmaxf(aymin, gc[g * 4 + 0]);
-    const float ix0 = fmaxf(axmin, gc[g * 4 + 1]);
-    const float iy1 = fminf(aymax, gc[g * 4 + 2]);
-    const float ix1 = fminf(axmax, gc[g * 4 + 3]);
-    const float hh = fmaxf(iy1 - iy0, 0.f);
-    const float ww = fmaxf(ix1 - ix0, 0.f);
-    const float inter = hh * ww;
-    const float uni = vol_a - inter + gv[g];  // (vol_anchors - inter_vol) + vol_gt
-    const float iou = inter / uni;
-    if (g == 0 || iou > best) {  // tf.argmax: first maximal index wins
-      best = iou;
-      idx = g;
+    for (int g = 0; g < n; ++g) {
+      const float iou = jaccard_ref(ac, vol_a, gc + g * 4, gv[g]);
+      if (g == 0 || iou > best) {  // tf.argmax: first maximal index wins
+        best = iou;
+        idx = g;
+      }
     }
-  }
   }
   // tf.greater_equal (net_tools.py:406); NEAREST_NEIGHBOR: pos_mask = ones (net_tools.py:375)
   const bool pos = n > 0 && (NN || best >= li.thr[lvl]);
@@ -150,7 +130,7 @@ __global__ void __launch_bounds__(256) match_anchors_kernel(const float* __restr
 // grid: x over (image, anchor-in-level) pairs of one level, y = level.
 template <typename T>
 __global__ void __launch_bounds__(256) smoothl1_kernel(const T* __restrict__ pred, const float* __restrict__ target,
-                                                       const int* __restrict__ mask, LevelInfo li, float inv_scale,
+                                                       const int* __restrict__ mask, Levels li, float inv_scale,
                                                        T* __restrict__ grad, float* __restrict__ grad_t,
                                                        float* __restrict__ slab, int B, int A, int nbx) {
   __shared__ float red[4];
@@ -254,7 +234,7 @@ __global__ void __launch_bounds__(256) box_iou_loss_kernel(const float* __restri
                                                            const T* __restrict__ refine_out,
                                                            const T* __restrict__ det_out,
                                                            const float* __restrict__ cbox,
-                                                           const int* __restrict__ det_pos, LevelInfo li, int kind,
+                                                           const int* __restrict__ det_pos, Levels li, int kind,
                                                            float gscale, T* __restrict__ grad,
                                                            float* __restrict__ slab, int B, int A, int nbx) {
   __shared__ float red[4];
@@ -276,27 +256,18 @@ __global__ void __launch_bounds__(256) box_iou_loss_kernel(const float* __restri
       load_row4<T, VEC>(det_out + o * 4, sb);
 #pragma unroll
       for (int k = 0; k < 4; ++k) s[k] = s[k] + sb[k];  // refine_out + det_out, as rod_decode
-      const float cy = s[0] * az[2] + az[0], cx = s[1] * az[3] + az[1];
-      const float h = exp_cr(s[2]) * az[2], w = exp_cr(s[3]) * az[3];
-      const float py0 = cy - h / 2.f, px0 = cx - w / 2.f, py1 = cy + h / 2.f, px1 = cx + w / 2.f;
-      const float gy0 = gz[0] - gz[2] / 2.f, gx0 = gz[1] - gz[3] / 2.f;
-      const float gy1 = gz[0] + gz[2] / 2.f, gx1 = gz[1] + gz[3] / 2.f;
-      // jaccard with det_targets_kernel's operations
-      const float ph = py1 - py0, pw = px1 - px0;
-      const float ap = pw * ph;
-      const float ihr = fminf(py1, gy1) - fmaxf(py0, gy0);
-      const float iwr = fminf(px1, gx1) - fmaxf(px0, gx0);
-      const float ih = fmaxf(ihr, 0.f), iw = fmaxf(iwr, 0.f);
-      const float I = ih * iw;
-      const float U = ap - I + (gy1 - gy0) * (gx1 - gx0);
-      const float iou = I / U;
+      // the predicted box and its IoU, by the helpers rod_decode and rod_det_targets call
+      const f32x4 z = decode_center(az, s);
+      const f32x4 pc = center_to_corner(z), gc = center_to_corner(gz);
+      const Jaccard j = jaccard_ref_parts(pc, vol_anchor(pc), gc, vol_gt(gc));
+      const float I = j.inter, U = j.uni, iou = j.iou;
       rl = 1.f - iou;
       const float q = I / (U * U);
       float d_I = -(1.f / U + q), d_ap = q;  // d(1 - iou) / d(I, area of the prediction)
       float d_eh = 0.f, d_ew = 0.f, d_cy = 0.f, d_cx = 0.f, d_h = 0.f, d_w = 0.f;
       if (kind != 0) {
         // the enclosing box: height, width, area C, squared diagonal c2
-        const float eh = fmaxf(py1, gy1) - fminf(py0, gy0), ew = fmaxf(px1, gx1) - fminf(px0, gx0);
+        const float eh = fmaxf(pc[2], gc[2]) - fminf(pc[0], gc[0]), ew = fmaxf(pc[3], gc[3]) - fminf(pc[1], gc[1]);
         if (kind == 1) {
           const float C = eh * ew;
           rl = rl + (C - U) / C;
@@ -307,7 +278,7 @@ __global__ void __launch_bounds__(256) box_iou_loss_kernel(const float* __restri
           d_ew = dC * eh;
         } else {
           const float c2 = eh * eh + ew * ew;
-          const float dy = cy - gz[0], dx = cx - gz[1];
+          const float dy = z[0] - gz[0], dx = z[1] - gz[1];
           const float rho2 = dy * dy + dx * dx;
           rl = rl + rho2 / c2;
           const float d_c2 = -(rho2 / (c2 * c2)), ir = 1.f / c2;
@@ -317,6 +288,7 @@ __global__ void __launch_bounds__(256) box_iou_loss_kernel(const float* __restri
           d_cx = ir * (2.f * dx);
           if (kind == 3) {
             const float k4 = 0.40528473456935109f;  // 4 / pi^2
+            const float h = z[2], w = z[3];
             const float dat = atan_cr(gz[3] / gz[2]) - atan_cr(w / h);
             const float v = k4 * (dat * dat);
             const float alpha = v == 0.f ? 0.f : v / ((1.f - iou) + v);  // a constant in the gradient
@@ -327,27 +299,11 @@ __global__ void __launch_bounds__(256) box_iou_loss_kernel(const float* __restri
           }
         }
       }
-      // max / min / max(., 0) with det_targets_bwd_kernel's rule, the prediction first
-      const float d_ih = ihr >= 0.f ? d_I * iw : 0.f;
-      const float d_iw = iwr >= 0.f ? d_I * ih : 0.f;
-      float d_py1 = py1 <= gy1 ? d_ih : 0.f, d_py0 = py0 >= gy0 ? -d_ih : 0.f;
-      float d_px1 = px1 <= gx1 ? d_iw : 0.f, d_px0 = px0 >= gx0 ? -d_iw : 0.f;
-      d_py1 += py1 >= gy1 ? d_eh : 0.f;
-      d_py0 += py0 <= gy0 ? -d_eh : 0.f;
-      d_px1 += px1 >= gx1 ? d_ew : 0.f;
-      d_px0 += px0 <= gx0 ? -d_ew : 0.f;
-      d_px1 += d_ap * ph;
-      d_px0 -= d_ap * ph;
-      d_py1 += d_ap * pw;
-      d_py0 -= d_ap * pw;
-      d_cy = d_cy + (d_py0 + d_py1);
-      d_cx = d_cx + (d_px0 + d_px1);
-      d_h = d_h + (d_py1 - d_py0) / 2.f;
-      d_w = d_w + (d_px1 - d_px0) / 2.f;
-      g[0] = d_cy * az[2] * gscale;
-      g[1] = d_cx * az[3] * gscale;
-      g[2] = d_h * h * gscale;
-      g[3] = d_w * w * gscale;
+      const f32x4 dj = jaccard_ref_bwd<true>(pc, gc, j, d_I, d_ap, d_eh, d_ew);
+      const f32x4 dz = {d_cy + dj[0], d_cx + dj[1], d_h + dj[2], d_w + dj[3]};
+      const f32x4 go = decode_center_bwd(dz, az, z);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) g[k] = go[k] * gscale;
     }
     if (grad) store_row4<T, VEC>(grad + o * 4, g);
   }
@@ -363,19 +319,7 @@ __global__ void boxes_convert_kernel(const float* __restrict__ in, float* __rest
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const f32x4 v = *(const f32x4*)(in + i * 4);
-  f32x4 o;
-  if (to_center) {  // [ymin,xmin,ymax,xmax] -> [cy,cx,h,w]
-    o[0] = (v[0] + v[2]) / 2.f;
-    o[1] = (v[1] + v[3]) / 2.f;
-    o[2] = v[2] - v[0];
-    o[3] = v[3] - v[1];
-  } else {          // [cy,cx,h,w] -> [ymin,xmin,ymax,xmax]
-    o[0] = v[0] - v[2] / 2.f;
-    o[1] = v[1] - v[3] / 2.f;
-    o[2] = v[0] + v[2] / 2.f;
-    o[3] = v[1] + v[3] / 2.f;
-  }
-  *(f32x4*)(out + i * 4) = o;
+  *(f32x4*)(out + i * 4) = to_center ? corner_to_center(v) : center_to_corner(v);
 }
 
 // dst[r, c] = src[r, c] for a rows x cols block with independent row strides (bytes)
@@ -392,14 +336,20 @@ __global__ void copy2d_kernel(const char* __restrict__ src, long sld, char* __re
   }
 }
 
-static int fill_levels(LevelInfo& li, const int* lvl_off, const float* thr, int L, int A) {
-  ROD_CHECK_ARG(L >= 1 && L <= MAXL, "levels: L=%d out of range [1,%d]", L, MAXL);
-  li.L = L;
-  for (int i = 0; i <= MAXL; ++i) li.off[i] = i <= L ? lvl_off[i] : A;
-  for (int i = 0; i < MAXL; ++i) li.thr[i] = (thr && i < L) ? thr[i] : 0.f;
-  ROD_CHECK_ARG(li.off[0] == 0 && li.off[L] == A, "levels: offsets must span [0, A]");
-  for (int i = 0; i < L; ++i) ROD_CHECK_ARG(li.off[i] <= li.off[i + 1], "levels: offsets must be monotone");
-  return 0;
+// both matching entries: NN picks the kernel and makes thr optional
+template <bool NN>
+static int match_anchors(const char* who, const float* anc_corner, const float* anc_center, const int* lvl_off,
+                         const float* thr, int L, const float* gt, const int* gt_lbl, const int* gt_n, float* out_off,
+                         float* out_cbox, int* out_lbl, int* out_pos, int B, int A, int G, void* stream) {
+  ROD_CHECK_ARG(B > 0 && A > 0 && G > 0, "%s: bad shape B=%d A=%d G=%d", who, B, A, G);
+  ROD_CHECK_ARG(G <= 4096, "%s: G=%d exceeds 4096", who, G);
+  ROD_CHECK_ARG(NN || thr, "%s: thr is a host array and must be given", who);
+  Levels li;
+  if (int rc = fill_levels(li, lvl_off, thr, L, A)) return rc;
+  size_t lds = (size_t)G * 10 * sizeof(float);
+  hipLaunchKernelGGL(match_anchors_kernel<NN>, dim3(cdiv(A, 256), B), dim3(256), lds, ROD_STREAM(stream), anc_corner,
+                     anc_center, li, gt, gt_lbl, gt_n, out_off, out_cbox, out_lbl, out_pos, A, G);
+  return check_launch(who);
 }
 
 }  // namespace rod
@@ -411,34 +361,18 @@ extern "C" {
 int rod_match_anchors(const float* anc_corner, const float* anc_center, const int* lvl_off, const float* thr, int L,
                       const float* gt, const int* gt_lbl, const int* gt_n, float* out_off, float* out_cbox,
                       int* out_lbl, int* out_pos, int B, int A, int G, void* stream) {
-  ROD_CHECK_ARG(B > 0 && A > 0 && G > 0, "rod_match_anchors: bad shape B=%d A=%d G=%d", B, A, G);
-  ROD_CHECK_ARG(G <= 4096, "rod_match_anchors: G=%d exceeds 4096", G);
-  ROD_CHECK_ARG(lvl_off && thr, "rod_match_anchors: lvl_off/thr are host arrays and must be given");
-  LevelInfo li;
-  int e = fill_levels(li, lvl_off, thr, L, A);
-  if (e) return e;
-  size_t lds = (size_t)G * 10 * sizeof(float);
-  hipLaunchKernelGGL(match_anchors_kernel<false>, dim3(cdiv(A, 256), B), dim3(256), lds, ROD_STREAM(stream),
-                     anc_corner, anc_center, li, gt, gt_lbl, gt_n, out_off, out_cbox, out_lbl, out_pos, A, G);
-  return check_launch("rod_match_anchors");
+  return match_anchors<false>("rod_match_anchors", anc_corner, anc_center, lvl_off, thr, L, gt, gt_lbl, gt_n, out_off,
+                              out_cbox, out_lbl, out_pos, B, A, G, stream);
 }
 
 int rod_match_anchors_nn(const float* anc_corner, const float* anc_center, const int* lvl_off, int L, const float* gt,
                          const int* gt_lbl, const int* gt_n, float* out_off, float* out_cbox, int* out_lbl,
                          int* out_pos, int B, int A, int G, void* stream) {
-  ROD_CHECK_ARG(B > 0 && A > 0 && G > 0, "rod_match_anchors_nn: bad shape B=%d A=%d G=%d", B, A, G);
-  ROD_CHECK_ARG(G <= 4096, "rod_match_anchors_nn: G=%d exceeds 4096", G);
-  ROD_CHECK_ARG(lvl_off, "rod_match_anchors_nn: lvl_off is a host array and must be given");
-  LevelInfo li;
-  int e = fill_levels(li, lvl_off, nullptr, L, A);
-  if (e) return e;
-  size_t lds = (size_t)G * 10 * sizeof(float);
-  hipLaunchKernelGGL(match_anchors_kernel<true>, dim3(cdiv(A, 256), B), dim3(256), lds, ROD_STREAM(stream),
-                     anc_corner, anc_center, li, gt, gt_lbl, gt_n, out_off, out_cbox, out_lbl, out_pos, A, G);
-  return check_launch("rod_match_anchors_nn");
+  return match_anchors<true>("rod_match_anchors_nn", anc_corner, anc_center, lvl_off, nullptr, L, gt, gt_lbl, gt_n,
+                             out_off, out_cbox, out_lbl, out_pos, B, A, G, stream);
 }
 
-static int smoothl1_nbx(int B, const LevelInfo& li) {
+static int smoothl1_nbx(int B, const Levels& li) {
   long mx = 1;
   for (int l = 0; l < li.L; ++l) mx = std::max<long>(mx, (long)B * (li.off[l + 1] - li.off[l]));
   return cdiv(mx, 256);
@@ -455,16 +389,17 @@ int rod_smoothl1_masked(const void* pred, const float* target, const int* mask, 
   ROD_CHECK_ARG(B > 0 && A > 0, "rod_smoothl1_masked: bad shape");
   ROD_CHECK_ARG(scale != 0.f, "rod_smoothl1_masked: scale must be non-zero");
   ROD_CHECK_ARG(workspace && loss_lvl, "rod_smoothl1_masked: workspace/loss_lvl NULL");
-  LevelInfo li;
-  int e = fill_levels(li, lvl_off, nullptr, L, A);
-  if (e) return e;
+  Levels li;
+  if (int rc = fill_levels(li, lvl_off, nullptr, L, A)) return rc;
   const int nbx = smoothl1_nbx(B, li);
   const float inv = 1.0f / scale;
   hipStream_t s = ROD_STREAM(stream);
-  ROD_DISPATCH_DTYPE(dtype, {
+  auto run = [&](auto tt) {
+    typedef decltype(tt) T;
     hipLaunchKernelGGL(smoothl1_kernel<T>, dim3(nbx, L), dim3(256), 0, s, (const T*)pred, target, mask, li, inv,
                        (T*)grad, grad_target, (float*)workspace, B, A, nbx);
-  });
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_smoothl1_masked: unsupported dtype code %d", dtype);
   hipLaunchKernelGGL(level_sum_finalize_kernel, dim3(1), dim3(256), 0, s, (const float*)workspace, nbx, L, 1.f, scale,
                      loss_lvl);
   return check_launch("rod_smoothl1_masked");
@@ -482,10 +417,8 @@ int rod_box_iou_loss(const float* anc_center, const void* refine_out, const void
   ROD_CHECK_ARG(weight >= 0.f && weight <= 3.402823466e38f, "rod_box_iou_loss: weight must be finite and >= 0, got %g",
                 (double)weight);
   ROD_CHECK_ARG(dtype == ROD_F32 || dtype == ROD_BF16, "rod_box_iou_loss: unsupported dtype code %d", dtype);
-  ROD_CHECK_ARG(lvl_off, "rod_box_iou_loss: lvl_off is a host array and must be given");
-  LevelInfo li;
-  int e = fill_levels(li, lvl_off, nullptr, L, A);
-  if (e) return e;
+  Levels li;
+  if (int rc = fill_levels(li, lvl_off, nullptr, L, A)) return rc;
   ROD_CHECK_ARG(anc_center && refine_out && det_out && cbox && det_pos,
                 "rod_box_iou_loss: anc_center/refine_out/det_out/cbox/det_pos NULL");
   ROD_CHECK_ARG(workspace && loss_lvl, "rod_box_iou_loss: workspace/loss_lvl NULL");
@@ -528,15 +461,10 @@ int rod_copy2d(const void* src, long src_ld_bytes, void* dst, long dst_ld_bytes,
   const int wb = (al & 15) == 0 ? 16 : ((al & 3) == 0 ? 4 : 1);
   const long chunks = cols_bytes / wb;
   const int grid = (int)std::min<long>(cdivl(rows * chunks, 256), 8192);
-  if (wb == 16)
-    hipLaunchKernelGGL(copy2d_kernel<16>, dim3(grid), dim3(256), 0, s, (const char*)src, src_ld_bytes, (char*)dst,
+  sel_int<16, 4, 1>(wb, [&](auto WB) {
+    hipLaunchKernelGGL(copy2d_kernel<WB>, dim3(grid), dim3(256), 0, s, (const char*)src, src_ld_bytes, (char*)dst,
                        dst_ld_bytes, rows, chunks);
-  else if (wb == 4)
-    hipLaunchKernelGGL(copy2d_kernel<4>, dim3(grid), dim3(256), 0, s, (const char*)src, src_ld_bytes, (char*)dst,
-                       dst_ld_bytes, rows, chunks);
-  else
-    hipLaunchKernelGGL(copy2d_kernel<1>, dim3(grid), dim3(256), 0, s, (const char*)src, src_ld_bytes, (char*)dst,
-                       dst_ld_bytes, rows, chunks);
+  });
   return check_launch("rod_copy2d");
 }
 

@@ -29,7 +29,7 @@ are M times them.
 import numpy as np
 
 KINDS = {'iou': 0, 'giou': 1, 'diou': 2, 'ciou': 3}
-MAXL = 8                     # the library's maximum level count (csrc/targets.hip)
+MAXL = 8                     # the library's maximum level count (csrc/box_common.h)
 # measured by tests/test_boxloss_host.py::test_float32_restatement_error and rounded up: the worst case is
 # `thin` (2.11e-5 / 1.62e-6: a box 0.01 wide at a coordinate of 0.5 loses 6 bits in cx +- w/2), the
 # others stay below 4.1e-6 / 1.5e-7

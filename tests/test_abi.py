@@ -39,6 +39,21 @@ def test_invalid_arguments_raise_with_message():
                   None, None, None, None, None, None, None, 1, 10, 4, None)
 
 
+def test_level_offsets_must_be_monotone():
+    """Every entry that takes a level table fills it through one check set: the ODM target and
+    classifier-loss entries reject non-monotone offsets too (the ODM targets look a level up by them)."""
+    lvl, thr, buf = np.array([0, 5, 3, 10], np.int32), np.zeros(3, np.float32), np.zeros(1, np.float32)
+    for name, args in (
+            ('rod_det_targets', (None,) * 6 + (lvl, thr, 3, None, None, None, None, 1, 10, 0, None)),
+            ('rod_softmax_ce_hnm', (None,) * 4 + (lvl, 3, 1.0, None, None, None, 1, 10, 4, 0, None)),
+            ('rod_iou_factor_bwd', (None,) * 4 + (lvl, 3, 1.0, buf, 1, 10, 4, 0, None)),
+            ('rod_hnm_loss', (None,) * 4 + (lvl, 3, 1.0, None, None, None, None, 1, 10, 4, 0, None)),
+            ('rod_smoothl1_masked', (None,) * 3 + (lvl, 3, 1.0, buf, None, None, buf, 1, 10, 0, None)),
+            ('rod_match_anchors_nn', (None, None, lvl, 3) + (None,) * 7 + (1, 10, 4, None))):
+        with pytest.raises(RuntimeError, match='levels: offsets must be monotone'):
+            _abi.call(name, *args)
+
+
 def test_workspace_queries_are_host_only():
     assert _abi.query('rod_bn_stats_workspace', 1000, 64) > 0
     assert _abi.query('rod_conv_wgrad_workspace', 2, 16, 16, 32, 64, 3) >= 4 * 64 * 9 * 32
