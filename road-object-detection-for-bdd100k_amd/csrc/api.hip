@@ -172,8 +172,7 @@ void slab_sum(const float* slab, float* out, int nslab, long n, hipStream_t s, b
   if (deferrable && g_slab_defer.load()) {
     std::lock_guard<std::mutex> lk(g_slab_mu);
     if (!g_slab_jobs) g_slab_jobs = new std::vector<SlabJob>();
-    static const bool vec_off = getenv("ROD_SLAB_VEC") && atoi(getenv("ROD_SLAB_VEC")) == 0;  // A/B switch
-    const int vec = !vec_off && n % 4 == 0 && ((uintptr_t)slab & 15) == 0 ? 4 : 1;
+    const int vec = n % 4 == 0 && ((uintptr_t)slab & 15) == 0 ? 4 : 1;
     g_slab_jobs->push_back(SlabJob{slab, out, n, nslab, cb, vec});
     return;
   }
@@ -360,9 +359,12 @@ int rod_normalize_image(const void* img_u8, void* out, long n, int out_dtype, vo
   if (n == 0) return 0;
   ROD_CHECK_ARG(((uintptr_t)img_u8 & 3) == 0, "rod_normalize_image: input must be 4-byte aligned");
   int blocks = cdiv(cdivl(n, 4), 256);
-  ROD_DISPATCH_DTYPE(out_dtype, hipLaunchKernelGGL(normalize_image_kernel<T>, dim3(blocks), dim3(256),
-                                                   0, ROD_STREAM(stream), (const uint8_t*)img_u8,
-                                                   (T*)out, n));
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
+    hipLaunchKernelGGL(normalize_image_kernel<T>, dim3(blocks), dim3(256), 0, ROD_STREAM(stream),
+                       (const uint8_t*)img_u8, (T*)out, n);
+  };
+  ROD_CHECK_ARG(sel_dtype(out_dtype, run), "rod_normalize_image: unsupported dtype code %d", out_dtype);
   return check_launch("rod_normalize_image");
 }
 

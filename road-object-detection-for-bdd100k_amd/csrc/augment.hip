@@ -362,8 +362,11 @@ int rod_augment_images(const void* src, const int64_t* src_off, const int32_t* s
   hipLaunchKernelGGL(aug_contrast_sums_kernel, dim3(nblk, B), dim3(256), 0, s, p, partial, nblk);
   hipLaunchKernelGGL(aug_contrast_mean_kernel, dim3(B), dim3(256), 0, s, partial, mean, nblk, npix);
   const int per_img = (int)min((long)4096, (npix / 4 + 255) / 256 + 1);
-  ROD_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(aug_apply_kernel<T>, dim3(per_img, B), dim3(256), 0, s, p, mean,
-                                               (T*)out, normalize));
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
+    hipLaunchKernelGGL(aug_apply_kernel<T>, dim3(per_img, B), dim3(256), 0, s, p, mean, (T*)out, normalize);
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_augment_images: unsupported dtype code %d", dtype);
   return check_launch("rod_augment_images");
 }
 

@@ -193,24 +193,16 @@ constexpr int MERGE_T = 1024;  // threads per merge block
 struct MergePlan {
   int CB, PL, slice;
 };
-static MergePlan merge_plan(int C, int nparts) {
-  // ROD_MERGE_LANE_PARTS (diagnosis switch): parts per lane per level (default 16) — a different
-  // slice grouping of the same fixed-order f64 merge
-  static const int lane_parts = getenv("ROD_MERGE_LANE_PARTS") ? atoi(getenv("ROD_MERGE_LANE_PARTS")) : 16;
-  const int lp = lane_parts > 0 ? lane_parts : 16;
+static MergePlan merge_plan(int C) {
+  constexpr int MERGE_LANE_PARTS = 16;   // parts per lane per level: the slice grouping of the fixed-order f64 merge
   MergePlan p;
   p.CB = C < 64 ? C : 64;   // 64 channels x 16+ part lanes per block
-  // ROD_MERGE_ONE_LEVEL=1 (opt-in): one level wherever it can — fewer channels per block (more
-  // part lanes) until one slice of <= 16 parts a lane holds every part, down to 2 channels (512
-  // lanes, 8192 parts): a 720p step's merges 124 -> 100 launches.  Its grouping differs from the
-  // fixed 64-channel plan (a rounding-level change of the merged statistics): the ALL-mode step
-  // tests accept it (the fp64 truth's own input-noise sensitivity covers the head-kink flip it
-  // causes), the 720p b8 fp32 step test (test_gpu_fullsize, no such probe: the fp64 truth takes
-  // minutes there) does not — refine/block_1 0.011 against a 0.0041 bar
-  static const bool one_level = getenv("ROD_MERGE_ONE_LEVEL") && atoi(getenv("ROD_MERGE_ONE_LEVEL")) == 1;
-  while (one_level && p.CB > 2 && (long)lp * (MERGE_T / p.CB) < nparts) p.CB = (p.CB + 1) / 2;
+  // One level wherever it can (fewer channels per block until one slice holds every part: a
+  // 720p step's merges 124 -> 100 launches) was tried and dropped: its grouping is a
+  // rounding-level change of the merged statistics that the 720p b8 fp32 step test
+  // (test_gpu_fullsize) does not accept — refine/block_1 0.011 against a 0.0041 bar
   p.PL = MERGE_T / p.CB;
-  p.slice = lp * p.PL;   // <= 16 parts per lane per level: short load chains
+  p.slice = MERGE_LANE_PARTS * p.PL;   // <= 16 parts per lane per level: short load chains
   return p;
 }
 
@@ -369,7 +361,7 @@ __global__ void __launch_bounds__(MERGE_T) bn_parts_merge_kernel(const float* pa
 
 // merge levels until one part remains; ws holds two ping-pong part buffers
 static size_t finalize_ws_bytes(int nparts, int C) {
-  const MergePlan p = merge_plan(C, nparts);
+  const MergePlan p = merge_plan(C);
   const int s1 = cdiv(nparts, p.slice);
   return s1 > 1 ? 2 * (size_t)s1 * 3 * C * sizeof(float) : 0;
 }
@@ -422,20 +414,15 @@ static unsigned* merge_counters(int n, hipStream_t s) {
 
 static void finalize_launch(const float* parts, int nparts, long M, int C, float eps, float decay, float* mean,
                             float* rstd, float* mm, float* mv, float* ws, hipStream_t s) {
-  const MergePlan p0 = merge_plan(C, nparts);
+  const MergePlan p0 = merge_plan(C);
   const int s1 = cdiv(nparts, p0.slice);
   float* buf[2] = {ws, ws ? ws + (size_t)s1 * 3 * C : nullptr};
   unsigned* cnt = nullptr;
   int slice2 = 0;
   if (s1 > 1) {
-    // two levels in one launch when the second is one slice with the same channel blocks
-    const MergePlan p1 = merge_plan(C, s1);
-    if (p1.CB == p0.CB && s1 <= p1.slice && (cnt = merge_counters(cdiv(C, p0.CB), s)) != nullptr) slice2 = p1.slice;
+    // two levels in one launch when the second is one slice
+    if (s1 <= p0.slice && (cnt = merge_counters(cdiv(C, p0.CB), s)) != nullptr) slice2 = p0.slice;
   }
-  static const bool dbg = getenv("ROD_DEBUG_MERGE") != nullptr;
-  if (dbg)
-    fprintf(stderr, "rod merge: nparts %d C %d M %ld levels %d launches %d\n", nparts, C, M, s1 > 1 ? 2 : 1,
-            s1 > 1 && cnt == nullptr ? 2 : 1);
   if (cnt != nullptr) {
     hipLaunchKernelGGL(bn_parts_merge_kernel, dim3(s1, cdiv(C, p0.CB)), dim3(MERGE_T), 0, s, parts, nparts, C, p0.CB,
                        p0.slice, buf[0], M, eps, decay, mean, rstd, mm, mv, cnt, slice2);
@@ -443,7 +430,7 @@ static void finalize_launch(const float* parts, int nparts, long M, int C, float
   }
   int k = 0;
   while (true) {
-    const MergePlan p = merge_plan(C, nparts);
+    const MergePlan p = merge_plan(C);
     const int S = cdiv(nparts, p.slice);
     hipLaunchKernelGGL(bn_parts_merge_kernel, dim3(S, cdiv(C, p.CB)), dim3(MERGE_T), 0, s, parts, nparts, C, p.CB, p.slice,
                        S > 1 ? buf[k] : nullptr, M, eps, decay, mean, rstd, mm, mv, (unsigned*)nullptr, 0);
@@ -514,7 +501,7 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const T* __restrict__ x, 
 // PIPE: the row batches are software-pipelined (batch k+1's loads issued before batch k's
 // arithmetic, ping-pong registers), so a wave keeps loads in flight while it computes; same
 // rows in the same order as the plain loop (sums bit-identical)
-template <typename T, bool VEC, bool PM = false, int U = 4, bool PIPE = false>
+template <typename T, bool VEC, bool PM = false, bool PIPE = false>
 __global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                             const float* __restrict__ mean,
                                                             const float* __restrict__ rstd,
@@ -523,6 +510,7 @@ __global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(const T* __restrict_
                                                             int ldx, int act, int CVb, int lanes, long chunk,
                                                             float* __restrict__ slab) {
   constexpr int V = VEC ? Vec16<T>::N : 1;
+  constexpr int U = 4;   // rows in flight per lane
   extern __shared__ __attribute__((aligned(16))) float red[];  // [2][256][V]
   const int tid = threadIdx.x;
   const int cvl = tid % CVb, pln = tid / CVb;
@@ -1107,7 +1095,8 @@ int rod_bn_bwd_apply(const void* dz, const void* y, const float* mean, const flo
                      const float* beta, const float* coef, void* dy, long M, int C, int act, int dtype, void* stream) {
   ROD_CHECK_ARG(M > 0 && C > 0 && coef != nullptr, "rod_bn_bwd_apply: bad arguments");
   hipStream_t s = ROD_STREAM(stream);
-  ROD_DISPATCH_DTYPE(dtype, {
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
     const bool vec = vec_ok<T>(C, {{dz, C}, {y, C}, {dy, C}});
     const int V = vec ? Vec16<T>::N : 1;
     const int blocks = const_channel_blocks(
@@ -1119,7 +1108,8 @@ int rod_bn_bwd_apply(const void* dz, const void* y, const float* mean, const flo
     else
       hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false>), dim3(blocks), dim3(256), 0, s, (const T*)dz, (const T*)y,
                          mean, rstd, gamma, beta, coef, (T*)dy, M, C, C, C, C, act);
-  });
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_bn_bwd_apply: unsupported dtype code %d", dtype);
   return check_launch("rod_bn_bwd_apply");
 }
 
@@ -1173,8 +1163,12 @@ int rod_bn_stats(const void* x, long M, int C, int ldx, float eps, float decay, 
   ROD_CHECK_ARG((moving_mean == nullptr) == (moving_var == nullptr), "rod_bn_stats: moving stats mismatch");
   ROD_CHECK_ARG(workspace != nullptr, "rod_bn_stats: workspace is NULL");
   hipStream_t s = ROD_STREAM(stream);
-  ROD_DISPATCH_DTYPE(dtype, stats_launch<T>(vec_ok<T>(C, {{x, ldx}}), x, M, C, ldx, eps, decay, mean, rstd,
-                                            moving_mean, moving_var, (float*)workspace, s));
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
+    stats_launch<T>(vec_ok<T>(C, {{x, ldx}}), x, M, C, ldx, eps, decay, mean, rstd, moving_mean, moving_var,
+                    (float*)workspace, s);
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_bn_stats: unsupported dtype code %d", dtype);
   return check_launch("rod_bn_stats");
 }
 
@@ -1196,8 +1190,12 @@ int rod_bn_apply(const void* x, const float* mean, const float* rstd, const floa
   if (ldr == 0) ldr = C;
   ROD_CHECK_ARG(ldx >= C && ldy >= C && ldr >= C, "rod_bn_apply: leading dim < C");
   hipStream_t s = ROD_STREAM(stream);
-  ROD_DISPATCH_DTYPE(dtype, apply_launch<T>(vec_ok<T>(C, {{x, ldx}, {y, ldy}, {residual, ldr}}), x, mean, rstd,
-                                            gamma, beta, residual, y, M, C, ldx, ldr, ldy, act, s));
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
+    apply_launch<T>(vec_ok<T>(C, {{x, ldx}, {y, ldy}, {residual, ldr}}), x, mean, rstd, gamma, beta, residual, y, M, C,
+                    ldx, ldr, ldy, act, s);
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_bn_apply: unsupported dtype code %d", dtype);
   return check_launch("rod_bn_apply");
 }
 
@@ -1214,36 +1212,28 @@ int rod_bn_bwd_reduce(const void* dz, const void* y, const float* mean, const fl
   ROD_CHECK_ARG(workspace != nullptr, "rod_bn_bwd_reduce: workspace is NULL");
   hipStream_t s = ROD_STREAM(stream);
   float* slab = (float*)workspace;
-  ROD_DISPATCH_DTYPE(dtype, {
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
     const bool vec = vec_ok<T>(C, {{dz, C}, {y, C}});
     if (small_ok(M, C / (vec ? Vec16<T>::N : 1))) {
       small_launch<T>(vec, dz, y, mean, rstd, gamma, beta, M, C, act, dgamma, dbeta, coef, nullptr, s);
-      return check_launch("rod_bn_bwd_reduce");
+      return;
     }
     // the backward reduce aims at 512 blocks (fewer, longer row chunks per block than the
-    // statistics' 1024: tools/bn_bench.py total 3558 -> 3455 us, 460800 x 192 208 -> 182 us);
-    // ROD_BN_RED_WANT overrides (A/B switch).  <= the 1024 plan's blocks, so the workspace
-    // bound (max_nbx) holds
-    static const long red_want = getenv("ROD_BN_RED_WANT") ? atol(getenv("ROD_BN_RED_WANT")) : 512;
-    RedPlan pl = red_plan<T>(M, C, vec, std::min<long>(red_want, 1024));
+    // statistics' 1024: tools/bn_bench.py total 3558 -> 3455 us, 460800 x 192 208 -> 182 us).
+    // <= the 1024 plan's blocks, so the workspace bound (max_nbx) holds
+    constexpr long BN_RED_WANT = 512;
+    RedPlan pl = red_plan<T>(M, C, vec, BN_RED_WANT);
     dim3 grid(pl.nbx, pl.cgroups);
     size_t lds = 2 * 256 * pl.V * sizeof(float);
-    // eight rows (16 loads) in flight per lane instead of four on the large tensors (>= 64 M
-    // elements: 1471 -> 1401 us at 7372800 x 96, 567 -> 541 us at 1843200 x 144 for reduce + apply,
-    // bit-identical; the mid-size ones lose, e.g. 28800 x 576 77 -> 85 us; tools/bn_bench.py).
-    // ROD_BN_RED_U=4 / 8 forces one form
-    static const int red_u = getenv("ROD_BN_RED_U") ? atoi(getenv("ROD_BN_RED_U")) : 0;
-    const bool u8 = red_u == 8 || (red_u == 0 && (long)M * C >= (64L << 20));
-    // the large tensors take the software-pipelined form (4-row batches, ping-pong): the step's
-    // shapes in tools/bn_bench.py 7372800 x 96 1459 -> 1369 us, x 32 480 -> 448, x 16 248 -> 231,
-    // 1843200 x 144 571 -> 528, 460800 x 192 203 -> 187 (reduce + apply, bit-identical); the
-    // mid-size ones are neutral to +3 us.  ROD_BN_RED_PIPE=0 keeps the 8-row form
-    static const bool red_pipe = !(getenv("ROD_BN_RED_PIPE") && atoi(getenv("ROD_BN_RED_PIPE")) == 0);
-    if (vec && u8 && red_pipe)
-      hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, true, false, 4, true>), grid, dim3(256), lds, s, (const T*)dz,
-                         (const T*)y, mean, rstd, gamma, beta, M, C, C, C, act, pl.CVb, pl.lanes, pl.chunk, slab);
-    else if (vec && u8)
-      hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, true, false, 8>), grid, dim3(256), lds, s, (const T*)dz,
+    // the large tensors (>= 64 M elements) take the software-pipelined form (4-row batches,
+    // ping-pong): the step's shapes in tools/bn_bench.py 7372800 x 96 1459 -> 1369 us, x 32
+    // 480 -> 448, x 16 248 -> 231, 1843200 x 144 571 -> 528, 460800 x 192 203 -> 187 (reduce +
+    // apply, bit-identical); the mid-size ones are neutral to +3 us.  Eight rows in flight per
+    // lane without the pipeline was measured first (1471 -> 1401 us at 7372800 x 96) and lost to it
+    const bool pipe = (long)M * C >= (64L << 20);
+    if (vec && pipe)
+      hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, true, false, true>), grid, dim3(256), lds, s, (const T*)dz,
                          (const T*)y, mean, rstd, gamma, beta, M, C, C, C, act, pl.CVb, pl.lanes, pl.chunk, slab);
     else if (vec)
       hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, true>), grid, dim3(256), lds, s, (const T*)dz, (const T*)y, mean,
@@ -1253,7 +1243,8 @@ int rod_bn_bwd_reduce(const void* dz, const void* y, const float* mean, const fl
                          rstd, gamma, beta, M, C, C, C, act, pl.CVb, pl.lanes, pl.chunk, slab);
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(C, 4)), dim3(256), 0, s, slab, pl.nbx, M, C, rstd, gamma,
                        dgamma, dbeta, coef);
-  });
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_bn_bwd_reduce: unsupported dtype code %d", dtype);
   return check_launch("rod_bn_bwd_reduce");
 }
 
@@ -1269,17 +1260,19 @@ int rod_bn_bwd(const void* dy, const void* x, const float* mean, const float* rs
   hipStream_t s = ROD_STREAM(stream);
   float* slab = (float*)workspace;
   float* coef = slab + (size_t)max_nbx(M, C) * 2 * C;  // after the largest slab
-  if (M <= SMALL_M && lddy == C && ldx == C && lddx == C) {
-    ROD_DISPATCH_DTYPE(dtype, {
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
+    if (M <= SMALL_M && lddy == C && ldx == C && lddx == C) {
       const bool vec = vec_ok<T>(C, {{dy, C}, {x, C}, {dx, C}});
       if (small_ok(M, C / (vec ? Vec16<T>::N : 1))) {
         small_launch<T>(vec, dy, x, mean, rstd, gamma, beta, M, C, act, dgamma, dbeta, coef, dx, s);
-        return check_launch("rod_bn_bwd");
+        return;
       }
-    });
-  }
-  ROD_DISPATCH_DTYPE(dtype, bwd_launch<T>(vec_ok<T>(C, {{dy, lddy}, {x, ldx}, {dx, lddx}}), dy, x, mean, rstd, gamma,
-                                          beta, dx, dgamma, dbeta, slab, coef, M, C, lddy, ldx, lddx, act, s));
+    }
+    bwd_launch<T>(vec_ok<T>(C, {{dy, lddy}, {x, ldx}, {dx, lddx}}), dy, x, mean, rstd, gamma, beta, dx, dgamma, dbeta,
+                  slab, coef, M, C, lddy, ldx, lddx, act, s);
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_bn_bwd: unsupported dtype code %d", dtype);
   return check_launch("rod_bn_bwd");
 }
 

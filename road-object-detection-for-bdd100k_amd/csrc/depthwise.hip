@@ -1244,12 +1244,10 @@ static dim3 dw_fwd_grid(int N, int Ho, int Wo, int C, int V) {
 // channel pack per thread: 16-byte (bf16 x8 / f32 x4) when C and the pointers allow it,
 // bf16 x4 (8-byte) when only C % 4 == 0, else scalar
 // `cap`: the forward and the filter gradient keep an fp32 3x3 window per channel, so they
-// use 4-channel packs; the data gradient 16-byte packs (ROD_DW_PACK overrides, A/B only)
+// use 4-channel packs; the data gradient 16-byte packs
 template <typename T>
 static int dw_pack(const void* a, const void* b, int C, int cap) {
   auto al = [&](uintptr_t n) { return (((uintptr_t)a | (uintptr_t)b) & (n - 1)) == 0; };
-  static const int force = getenv("ROD_DW_PACK") ? atoi(getenv("ROD_DW_PACK")) : 0;
-  if (force) cap = force;
   if (sizeof(T) == 2 && C % 8 == 0 && al(16) && cap >= 8) return 8;
   if (C % 4 == 0 && al(4 * sizeof(T))) return 4;
   return 1;
@@ -1284,8 +1282,7 @@ static void dw_fwd_launch(const void* x, const BnPro* pro, const float* w, void*
 // LDS-exchange forward: needs 16-byte packs (C % V == 0, 16-byte aligned x and y).
 template <typename T>
 static bool dw_lx_ok(const void* x, const void* y, int C) {
-  static const bool legacy = getenv("ROD_DW_LEGACY") != nullptr;  // A/B timing switch
-  return !legacy && C % Vec16<T>::N == 0 && ((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0;
+  return C % Vec16<T>::N == 0 && ((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0;
 }
 static long dw_lx_parts(int N, int Ho, int Wo, int C, int S, int V) {
   const DwTile t = dw_tile(N, Ho, Wo, C, S, V);
@@ -1317,8 +1314,7 @@ static long dw_fwd_lx_launch(const void* x, const BnPro* pro, const float* w, vo
 // the grid of the backward-data launch (phase-split kernel for stride 2): its block count is
 // the gred part count
 static dim3 dw_bwd_data_grid(int N, int H, int W, int C, int S, int pt, int pl, int V, bool* s2k) {
-  static const bool no_s2 = getenv("ROD_DEBUG_NOS2") != nullptr;  // debug bisection
-  *s2k = S == 2 && pt <= 1 && pl <= 1 && !no_s2;
+  *s2k = S == 2 && pt <= 1 && pl <= 1;
   if (*s2k) {
     const int Bc = (W - 1 + pl) / 2 + 1;
     const int Ar = (H - 1 + pt) / 2 + 1;
@@ -1422,7 +1418,7 @@ int rod_dw3x3_fwd(const void* x, const float* pro_mean, const float* pro_rstd, c
     const int V = pk == 8 ? (sizeof(T) == 2 ? 8 : 4) : pk;
     const dim3 g = dw_fwd_grid(N, Ho, Wo, C, V);
     // the fused statistics write one part per block; when that is not the count the caller
-    // sized the slab for (misaligned pointers, legacy switch), a separate pass writes them
+    // sized the slab for (misaligned pointers), a separate pass writes them
     const bool fuse = stat_parts && (long)g.x * g.y * g.z == nparts;
     dw_select<T>(stride, pk, [&](auto S, auto VP) {
       dw_fwd_launch<T, S, VP>(x, pp, w, y, fuse ? stat_parts : nullptr, N, H, W, C, pad_t, pad_l, Ho, Wo, s);
@@ -1585,214 +1581,10 @@ int rod_dw3x3_bwd_filter_bn(const void* x, const float* pro_mean, const float* p
 // bit-identical to the unfused chain; dw and the BN_e sums are reassociated (column tiles).
 // =====================================================================================
 
-template <typename T, int PACT, bool RED, int D = 3>
-__global__ void __launch_bounds__(256) dw3x3_bwd_fused_kernel(const T* __restrict__ ye, const T* __restrict__ dz,
-                                                              const T* __restrict__ yd, const float* __restrict__ w,
-                                                              T* __restrict__ dx, float* __restrict__ slab,
-                                                              float* __restrict__ gparts, int H, int W, int C,
-                                                              DwTile tl, BnPro pro, DwBwdBn bd) {
-  constexpr int V = 4;
-  typedef PackV<T, V> PK;
-  constexpr int XS = 2 * 2 * 256 * (int)sizeof(PK);  // x and dy slots, double buffered
-  constexpr int SS = 256 * V * 4;                     // per-tap column reduction
-  __shared__ __attribute__((aligned(16))) char smem[XS > SS ? XS : SS];
-  PK* xs = (PK*)smem;              // [2][256]
-  PK* dsl = xs + 2 * 256;          // [2][256]
-  const int tid = threadIdx.x;
-  const int CVb = tl.CVb, P = tl.P;
-  const int p = tid / CVb, cvb = tid - (tid / CVb) * CVb;
-  int bx, strip, n;
-  xcd_block(bx, strip, n);
-  const int cg = bx % tl.cgroups, ct = bx / tl.cgroups;
-  const int c = (cg * CVb + cvb) * V;
-  const int col = ct * tl.TWo + p - 1;                  // pads (1, 1): input column = output column
-  const bool comp = p >= 1 && p <= P - 2 && col < W;
-  const bool cok = p < P && col >= 0 && col < W;
-  const int ho0 = strip * tl.RB;
-  const int ho1 = ho0 + tl.RB < H ? ho0 + tl.RB : H;
-  const int xlo = ho0 - 1 > 0 ? ho0 - 1 : 0, xhi = ho1 < H - 1 ? ho1 : H - 1;  // rows of x / dy needed
-
-  float wr[9][V];
-#pragma unroll
-  for (int k = 0; k < 9; ++k)
-#pragma unroll
-    for (int v = 0; v < V; ++v) wr[k][v] = w[k * C + c + v];
-  DwIn<T, V, PACT> in;
-  in.init(pro, c);
-  float dsc[V], dsh[V], da[V], dmg[V], dmx[V], dmm[V];   // dmg / dmx / dmm: the apply's k1 / k0 / m
-#pragma unroll
-  for (int v = 0; v < V; ++v) {
-    bn_affine(bd.mean, bd.rstd, bd.gamma, bd.beta, c + v, dsc[v], dsh[v]);
-    da[v] = bd.coef[c + v];
-    bn_bwd_k<T>(da[v], bd.mean[c + v], bd.rstd[c + v], bd.coef[C + c + v], bd.coef[2 * C + c + v], dmg[v], dmx[v],
-                dmm[v]);
-  }
-  constexpr int RV = RED ? V : 1;
-  float emu[RV], ers[RV], sg[RV], sgx[RV];
-  if constexpr (RED) {
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-      emu[v] = pro.mean[c + v];
-      ers[v] = pro.rstd[c + v];
-      sg[v] = sgx[v] = 0.f;
-    }
-  }
-  const long nb = (long)n * H * W * C + c;
-  const T* yen = ye + nb;
-  const T* dzn = dz + nb;
-  const T* ydn = yd + nb;
-  T* dxn = dx + nb;
-
-  // prefetch ring of D steps: step q loads x row ho0-2+q and (dz, yd) of row ho0-1+q
-  PK rx[D], rz[D], ry[D];
-  bool okx[D], okd[D];
-  auto issue = [&](int k, int q) {
-    const int rho = ho0 - 2 + q;
-    okx[k] = cok && rho >= xlo && rho <= xhi;
-    okd[k] = cok && rho + 1 >= xlo && rho + 1 <= xhi;
-    if (okx[k]) rx[k].load(yen + ((long)rho * W + col) * C);
-    if (okd[k]) {
-      rz[k].load(dzn + ((long)(rho + 1) * W + col) * C);
-      ry[k].load(ydn + ((long)(rho + 1) * W + col) * C);
-    }
-  };
-  const int nst = ho1 - ho0 + 3;
-#pragma unroll
-  for (int k = 0; k < D; ++k) issue(k, k);
-  float acc[3][V], fa[9][V], q1[V], q2[V];
-#pragma unroll
-  for (int v = 0; v < V; ++v) {
-    acc[0][v] = acc[1][v] = acc[2][v] = 0.f;
-    q1[v] = q2[v] = 0.f;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) fa[k][v] = 0.f;
-  }
-  // D is a multiple of 3: the ring slot (q mod D) and the dx accumulator slot (q mod 3) are
-  // both compile-time under the unroll
-  static_assert(D % 3 == 0, "ring depth must be a multiple of 3");
-  for (int q0 = 0; q0 < nst; q0 += D) {
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      const int q = q0 + k;
-      const int rho = ho0 - 2 + q;
-      const int buf = q & 1;
-      const int k3 = k % 3;
-      // x row rho: the forward's input (prologue, rounded to T), 0 outside the rows needed
-      float xv[V], yraw[V];
-      {
-        in.cvt(rx[k], okx[k], xv);
-        if constexpr (PACT < 0) {
-#pragma unroll
-          for (int v = 0; v < V; ++v) xv[v] = okx[k] ? xv[v] : 0.f;
-        }
-#pragma unroll
-        for (int v = 0; v < V; ++v) yraw[v] = rx[k].get(v);
-      }
-      // dy row rho + 1: the BatchNorm-backward apply of BN_d, rounded to T
-      float dv[V];
-#pragma unroll
-      for (int v = 0; v < V; ++v) {
-        const float yv = ry[k].get(v);
-        const float z = fmaf(yv, dsc[v], dsh[v]);
-        const float g = rz[k].get(v) * act_grad(z, bd.act);
-        const float o = bn_bwd_apply1<T>(da[v], g, dmg[v], dmx[v], dmm[v], yv);
-        dv[v] = okd[k] ? to_f32(from_f32<T>(o)) : 0.f;
-      }
-      PK px, pd;
-#pragma unroll
-      for (int v = 0; v < V; ++v) {
-        px.set(v, xv[v]);
-        pd.set(v, dv[v]);
-      }
-      issue(k, q + D);
-      xs[buf * 256 + tid] = px;
-      dsl[buf * 256 + tid] = pd;
-      __syncthreads();
-      if (comp) {
-        const PK xl = xs[buf * 256 + tid - CVb], xr = xs[buf * 256 + tid + CVb];
-        const PK dl = dsl[buf * 256 + tid - CVb], dr = dsl[buf * 256 + tid + CVb];
-        // backward-data: dy row rho+1 is tap row 0 of dx row rho, 1 of rho+1, 2 of rho+2
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-          const int sl = (k3 + i) % 3;
-#pragma unroll
-          for (int v = 0; v < V; ++v) {
-            float a = acc[sl][v];
-            a = fmaf(dl.get(v), wr[i * 3 + 2][v], a);
-            a = fmaf(dv[v], wr[i * 3 + 1][v], a);
-            a = fmaf(dr.get(v), wr[i * 3][v], a);
-            acc[sl][v] = a;
-          }
-        }
-        // filter: x row rho with the strip's dy rows rho+1 (tap row 0), rho (1), rho-1 (2)
-        const bool own = rho + 1 >= ho0 && rho + 1 < ho1;
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-          const float f0 = own ? dv[v] : 0.f;
-          const float t0 = xl.get(v), t2 = xr.get(v);
-          fa[0][v] = fmaf(f0, t0, fa[0][v]);
-          fa[1][v] = fmaf(f0, xv[v], fa[1][v]);
-          fa[2][v] = fmaf(f0, t2, fa[2][v]);
-          fa[3][v] = fmaf(q1[v], t0, fa[3][v]);
-          fa[4][v] = fmaf(q1[v], xv[v], fa[4][v]);
-          fa[5][v] = fmaf(q1[v], t2, fa[5][v]);
-          fa[6][v] = fmaf(q2[v], t0, fa[6][v]);
-          fa[7][v] = fmaf(q2[v], xv[v], fa[7][v]);
-          fa[8][v] = fmaf(q2[v], t2, fa[8][v]);
-          q2[v] = q1[v];
-          q1[v] = f0;
-        }
-        // dx row rho is complete
-        if (rho >= ho0 && rho < ho1) {
-          PK o;
-#pragma unroll
-          for (int v = 0; v < V; ++v) o.set(v, acc[k3][v]);
-          o.store_out(dxn + ((long)rho * W + col) * C);
-          if constexpr (RED) {
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-              const float z = fmaf(yraw[v], in.sc[v], in.sh[v]);
-              const float g = o.get(v) * act_grad(z, pro.act);
-              sg[v] += g;
-              sgx[v] = fmaf(g, (yraw[v] - emu[v]) * ers[v], sgx[v]);
-            }
-          }
-        }
-#pragma unroll
-        for (int v = 0; v < V; ++v) acc[k3][v] = 0.f;
-      }
-    }
-  }
-
-  // per channel: sum over the computing columns (column order), tap by tap, then the BN_e sums
-  __syncthreads();
-  float* red = (float*)smem;
-  const int Cc = CVb * V;
-  const long part = ((long)n * tl.strips + strip) * tl.coltiles + ct;
-  auto colsum = [&](const float (&a)[V], float* dst) {
-#pragma unroll
-    for (int v = 0; v < V; ++v) red[tid * V + v] = comp ? a[v] : 0.f;
-    __syncthreads();
-    for (int e = tid; e < Cc; e += 256) {
-      const int cve = e / V, v = e - cve * V;
-      float s = 0.f;
-      for (int pp = 1; pp <= P - 2; ++pp) s += red[(pp * CVb + cve) * V + v];
-      dst[cg * Cc + e] = s;
-    }
-    __syncthreads();
-  };
-#pragma unroll
-  for (int k = 0; k < 9; ++k) colsum(fa[k], slab + (part * 9 + k) * C);
-  if constexpr (RED) {
-    colsum(sg, gparts + part * 2 * C);
-    colsum(sgx, gparts + part * 2 * C + C);
-  }
-}
-
-// Issue-lean form of dw3x3_bwd_fused_kernel (the default; ROD_DWF_V1=1 selects the one above).
-// Same engine, same per-element arithmetic and accumulation order (dx bit-identical), cut for
-// the instruction stream (tools/dwfused_bench.py PMC: the step was ~230 VALU + ~90 SALU per
-// barrier interval, 2 waves / SIMD, VALU-issue and latency bound):
+// The stride-1 kernel.  Its first form (per-lane conditions in the loop body, scalar f32 ops)
+// ran ~230 VALU + ~90 SALU per barrier interval at 2 waves / SIMD, VALU-issue and latency bound
+// (tools/dwfused_bench.py PMC), and is gone; this one keeps the engine, the per-element
+// arithmetic and the accumulation order (dx bit-identical) and is cut for the instruction stream:
 //   * per-lane conditions leave the loop body: every thread (halo columns included) loads a
 //     clamped, always-valid column, computes dx / filter / BN_e sums, and only the dx store is
 //     predicated on `comp`; halo sums are dropped by the column reduction as before.  Row
@@ -1823,16 +1615,17 @@ constexpr int DWPW_LD = 52;
 #define DW_QG_PW 6
 #endif   // LDS row stride (bf16) of the recomputed dz tile: <= 48 channels + pad
 
-// V = 2: the same tile with twice the threads (512 per block), each holding 2 channels — half the
-// per-thread weights, accumulators and BatchNorm constants, twice the waves in flight
-template <typename T, int PACT, bool RED, int BACT, int V = 4, int D = 3, bool PW = false>
+// V = 2 (bf16): the same tile with twice the threads (512 per block), each holding 2 channels —
+// half the per-thread weights, accumulators and BatchNorm constants, twice the waves in flight;
+// fp32 keeps V = 4.  The prefetch ring has D = 3 steps, one per dx accumulator row.
+template <typename T, int PACT, bool RED, int BACT, int V = 4, bool PW = false>
 __global__ void __launch_bounds__(1024 / V, PW ? 4 : 1) dw3x3_bwd_fused2_kernel(const T* __restrict__ ye, const T* __restrict__ dz,
                                                                const T* __restrict__ yd, const float* __restrict__ w,
                                                                T* __restrict__ dx, float* __restrict__ slab,
                                                                float* __restrict__ gparts, int H, int W, int C,
                                                                DwTile tl, BnPro pro, DwBwdBn bd, DwPw pw = DwPw{}) {
-  static_assert(D % 3 == 0, "the ring steps a multiple of the 3 accumulator rows");
-  static_assert(!PW || (V == 2 && D == 3 && sizeof(T) == 2), "PW: the bf16 2-channel form, 3-step ring");
+  constexpr int D = 3;
+  static_assert(!PW || (V == 2 && sizeof(T) == 2), "PW: the bf16 2-channel form");
   constexpr int VP = V / 2;  // V channels per thread = VP packed pairs
   constexpr int TB = 1024 / V;      // threads per block (the tile of the 4-channel plan)
   typedef PackV<T, V> PK;
@@ -1991,9 +1784,6 @@ __global__ void __launch_bounds__(1024 / V, PW ? 4 : 1) dw3x3_bwd_fused2_kernel(
 #pragma unroll
     for (int k = 0; k < D; ++k) {
       const int q = q0 + k;
-      if constexpr (D > 3) {  // the deep ring's tail: whole 3-step groups only (block-uniform), so
-        if (k % 3 == 0 && q >= nst) break;   // every path to the back-edge issued the same loads
-      }
       const int rho = ho0 - 2 + q;
       const int k3 = k % 3;
       const int buf = k3;
@@ -2155,14 +1945,18 @@ __global__ void __launch_bounds__(1024 / V, PW ? 4 : 1) dw3x3_bwd_fused2_kernel(
 // dy[a-1][b-1], in the order of dw3x3_bwd_data_s2_kernel (bit-identical dx); the filter pairs
 // dy[a] with x rows 2a-pt (tap row 0), 2a+1-pt (1) and dy[a-1] with 2a-pt (2), the third tap
 // column coming from the right neighbour's first column (LDS).
-template <typename T, int PACT, bool RED, int D = 3>
-__global__ void __launch_bounds__(256, 2) dw3x3_bwd_fused_s2_kernel(const T* __restrict__ ye, const T* __restrict__ dz,
-                                                                 const T* __restrict__ yd, const float* __restrict__ w,
-                                                                 T* __restrict__ dx, float* __restrict__ slab,
+// fp32 only (bf16 takes the packed kernel below), with a prefetch ring of one step.
+template <int PACT, bool RED>
+__global__ void __launch_bounds__(256, 2) dw3x3_bwd_fused_s2_kernel(const float* __restrict__ ye, const float* __restrict__ dz,
+                                                                 const float* __restrict__ yd, const float* __restrict__ w,
+                                                                 float* __restrict__ dx, float* __restrict__ slab,
                                                                  float* __restrict__ gparts, int H, int W, int C,
                                                                  int pt, int pl, int Ho, int Wo, DwTile tl, BnPro pro,
                                                                  DwBwdBn bd) {
-  constexpr int V = 4;
+  typedef float T;
+  // D: ring depth.  One step here (at 2 the bf16 form took 238 VGPRs and spilled); the D-sized
+  // arrays and loops below are the ring scaffolding shared in shape with the packed kernel
+  constexpr int V = 4, D = 1;
   typedef PackV<T, V> PK;
   constexpr int XS = 3 * 2 * 256 * (int)sizeof(PK);  // dy, x row 0, x row 1 slots, double buffered
   constexpr int SS = 256 * V * 4;
@@ -2393,7 +2187,7 @@ __global__ void __launch_bounds__(256, 2) dw3x3_bwd_fused_s2_kernel(const T* __r
 // ReLU6 gates as selects, the row exchange in fp32 pairs (no pack / unpack around the LDS trip)
 // with one LDS slot per step of the 2-step body (compile-time addresses), and the BN_e gate
 // taken from the prologue's own pre-activation.
-template <int PACT, bool RED, int BACT, int D = 2, int V = 4>
+template <int PACT, bool RED, int BACT, int V = 4>
 __global__ void __launch_bounds__(1024 / V, V == 4 ? 2 : 1) dw3x3_bwd_fused_s2p_kernel(
     const bf16_t* __restrict__ ye, const bf16_t* __restrict__ dz, const bf16_t* __restrict__ yd,
     const float* __restrict__ w, bf16_t* __restrict__ dx, float* __restrict__ slab, float* __restrict__ gparts, int H,
@@ -2402,7 +2196,7 @@ __global__ void __launch_bounds__(1024 / V, V == 4 ? 2 : 1) dw3x3_bwd_fused_s2p_
   constexpr int VP = V / 2;
   constexpr int TB = 1024 / V;   // threads per block: the 4-channel tile with V channels a thread
   typedef PackV<T, V> PK;
-  static_assert(D >= 2, "one LDS slot per step of the D-step body");
+  constexpr int D = 2;   // ring depth: one LDS slot per step of the D-step body
   // slots [D][3][256][VP] fp32 pairs: dy, x row 0, x row 1 (column ci0)
   constexpr int XS = D * 3 * TB * VP * (int)sizeof(dw_f2);
   constexpr int SS = (RED ? 11 : 9) * TB * V * 4;   // the epilogue's staged column sums
@@ -2696,25 +2490,22 @@ int rod_dw3x3_bwd_fused(const void* ye, const float* pro_mean, const float* pro_
   const BnPro pv{pro_mean, pro_rstd, pro_gamma, pro_beta, pro_act};
   const DwBwdBn bd{bn_mean, bn_rstd, bn_gamma, bn_beta, coef, bn_act};
   float* slab = (float*)workspace;
-  // A/B measurement switches, each read once; the defaults and what they measured:
-  //  * stride 1 runs the issue-lean kernel (fused2); ROD_DWF_V1=1 the first form (fused);
-  //  * both prefetch through a 3-step ring; ROD_DWF_RING=6 a 6-step one (3.27 vs 3.34 ms for the
-  //    first form over the step's bf16 shapes; with 2 channels it needs 131 VGPRs, 3 waves/SIMD);
-  //  * bf16 stride 1: 2 channels per thread in 512-thread blocks (122 VGPRs, 4 waves/SIMD: with
-  //    branch-free buffer I/O the ring's wait counts are exact); ROD_DWF_C2=0 the 4-channel form;
-  //  * bf16 stride 2: the packed kernel (s2p); ROD_DWF_S2P=0 the scalar one (s2), which fp32
-  //    always takes, with a ring of 2 steps for bf16 (238 VGPRs; 3 spill) and 1 for fp32;
-  //  * packed with a ReLU6 BN_d: 2 channels per thread in 512-thread blocks (116 VGPRs, 4 waves /
-  //    SIMD instead of 2 at 204: tools/dwfused_bench.py stride-2 shapes 1686 -> 1604 us, dx
-  //    bit-identical); ROD_DWF_S2P_V=4 the 4-channel form, ROD_DWF_S2P_D=3 a 3-step ring.
-  static const int ring = getenv("ROD_DWF_RING") && atoi(getenv("ROD_DWF_RING")) == 6 ? 6 : 3;
-  static const bool v1 = getenv("ROD_DWF_V1") && atoi(getenv("ROD_DWF_V1")) == 1;
-  static const bool c2 = !(getenv("ROD_DWF_C2") && atoi(getenv("ROD_DWF_C2")) == 0);
-  static const bool s2p = !(getenv("ROD_DWF_S2P") && atoi(getenv("ROD_DWF_S2P")) == 0);
-  static const bool s2p2 = !(getenv("ROD_DWF_S2P_V") && atoi(getenv("ROD_DWF_S2P_V")) == 4);
-  static const bool s2pd3 = getenv("ROD_DWF_S2P_D") && atoi(getenv("ROD_DWF_S2P_D")) == 3;
-  const int ba = bn_act == ROD_ACT_RELU6 ? ROD_ACT_RELU6 : DW_ACT_RT;   // BN_d's activation: inlined ReLU6 or run time
-  // PA: the input prologue's form; R: also sum BN_e's backward parts (needs the prologue)
+  // What runs, by storage type and stride (PA: the input prologue's form; R: also BN_e's sums):
+  //   bf16 stride 1   fused2, 2 channels per thread in 512-thread blocks, 3-step ring
+  //   fp32 stride 1   fused2, 4 channels per thread in 256-thread blocks, 3-step ring
+  //   bf16 stride 2   the packed kernel (s2p), 2-step ring: a ReLU6 BN_d with 2 channels per
+  //                   thread in 512-thread blocks, a run-time activation with 4 in 256
+  //   fp32 stride 2   the scalar kernel (s2), 1-step ring
+  // What was measured against them, and lost:
+  //   * a 6-step ring for stride 1: no gain at 4 channels per thread (226 VGPRs; 3.78 ms against
+  //     3.76 with 3 steps over the step's bf16 shapes), and with 2 channels it needs 131 VGPRs,
+  //     3 waves / SIMD instead of 4;
+  //   * 4 channels per thread for bf16 stride 1: the 2-channel form has 122 VGPRs, 4 waves / SIMD
+  //     (with branch-free buffer I/O the ring's wait counts are exact);
+  //   * the scalar kernel for bf16 stride 2, with a 2-step ring: 238 VGPRs and 3 spills;
+  //   * 4 channels per thread for the packed ReLU6 form: 204 VGPRs, 2 waves / SIMD against 116 and
+  //     4 (tools/dwfused_bench.py stride-2 shapes 1686 -> 1604 us, dx bit-identical), and a
+  //     3-step ring for it.
   auto go = [&](auto tag, auto PA, auto R) {
     typedef decltype(tag) T;
     constexpr bool BF = sizeof(T) == 2;
@@ -2722,38 +2513,19 @@ int rod_dw3x3_bwd_fused(const void* ye, const float* pro_mean, const float* pro_
       hipLaunchKernelGGL(kern, grid, dim3(block), 0, s, (const T*)ye, (const T*)dz, (const T*)yd, w, (T*)dx, slab,
                          gparts, H, W, C, tail...);
     };
+    const bool relu6 = bn_act == ROD_ACT_RELU6;   // BN_d's activation: inlined ReLU6, else read at run time
     if (stride == 2) {
-      if constexpr (BF) {
-        if (s2p && s2p2 && ba == ROD_ACT_RELU6) {
-          sel_int<2, 3>(s2pd3 ? 3 : 2, [&](auto D) {
-            launch(dw3x3_bwd_fused_s2p_kernel<PA, R, ROD_ACT_RELU6, D, 2>, 512, pad_t, pad_l, Ho, Wo, t, pv, bd);
-          });
-          return;
-        }
-        if (s2p) {
-          sel_int<ROD_ACT_RELU6, DW_ACT_RT>(ba, [&](auto BA) {
-            launch(dw3x3_bwd_fused_s2p_kernel<PA, R, BA, 2, 4>, 256, pad_t, pad_l, Ho, Wo, t, pv, bd);
-          });
-          return;
-        }
-      }
-      launch(dw3x3_bwd_fused_s2_kernel<T, PA, R, BF ? 2 : 1>, 256, pad_t, pad_l, Ho, Wo, t, pv, bd);
+      if constexpr (!BF)
+        launch(dw3x3_bwd_fused_s2_kernel<PA, R>, 256, pad_t, pad_l, Ho, Wo, t, pv, bd);
+      else if (relu6)
+        launch(dw3x3_bwd_fused_s2p_kernel<PA, R, ROD_ACT_RELU6, 2>, 512, pad_t, pad_l, Ho, Wo, t, pv, bd);
+      else
+        launch(dw3x3_bwd_fused_s2p_kernel<PA, R, DW_ACT_RT, 4>, 256, pad_t, pad_l, Ho, Wo, t, pv, bd);
       return;
     }
-    sel_int<3, 6>(ring, [&](auto D) {
-      if (v1) {
-        launch(dw3x3_bwd_fused_kernel<T, PA, R, D>, 256, t, pv, bd);
-        return;
-      }
-      sel_int<ROD_ACT_RELU6, DW_ACT_RT>(ba, [&](auto BA) {
-        if constexpr (BF) {
-          if (c2) {
-            launch(dw3x3_bwd_fused2_kernel<T, PA, R, BA, 2, D>, 512, t, pv, bd, DwPw{});
-            return;
-          }
-        }
-        launch(dw3x3_bwd_fused2_kernel<T, PA, R, BA, 4, D>, 256, t, pv, bd, DwPw{});
-      });
+    sel_int<ROD_ACT_RELU6, DW_ACT_RT>(relu6 ? ROD_ACT_RELU6 : DW_ACT_RT, [&](auto BA) {
+      constexpr int V = BF ? 2 : 4;
+      launch(dw3x3_bwd_fused2_kernel<T, PA, R, BA, V>, 1024 / V, t, pv, bd, DwPw{});
     });
   };
   sel_dtype(dtype, [&](auto tag) {
@@ -2802,7 +2574,7 @@ int rod_dw3x3_bwd_fused_pw(const void* ye, const float* pro_mean, const float* p
   const DwPw pw{(const bf16_t*)dyp, (const bf16_t*)wt1, cout};
   float* slab = (float*)workspace;
   sel_bool(gparts != nullptr, [&](auto R) {
-    hipLaunchKernelGGL((dw3x3_bwd_fused2_kernel<bf16_t, ROD_ACT_RELU6, R, ROD_ACT_RELU6, 2, 3, true>), grid,
+    hipLaunchKernelGGL((dw3x3_bwd_fused2_kernel<bf16_t, ROD_ACT_RELU6, R, ROD_ACT_RELU6, 2, true>), grid,
                        dim3(512), 0, s, (const bf16_t*)ye, (const bf16_t*)nullptr, (const bf16_t*)yd, w, (bf16_t*)dx,
                        slab, gparts, H, W, C, t, pv, bd, pw);
   });

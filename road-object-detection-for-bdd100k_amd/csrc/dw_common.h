@@ -106,11 +106,10 @@ inline DwTile dw_tile(int N, int Ho, int Wo, int C, int S, int V) {
   // against 8, 24: 468.5 / 467.8).  It regroups the statistic / filter partial sums (a
   // rounding-level change); round 2 kept 8 because the ALL-mode step test then moved — a kink
   // flip the fp64 truth itself shows under 1e-6 input noise, which that test now measures.
-  // Measurement switches: ROD_DW_WANT (target blocks, 1024), ROD_DW_RBMIN (minimum rows per block)
-  static const long want_blocks = getenv("ROD_DW_WANT") ? atol(getenv("ROD_DW_WANT")) : 1024;
-  static const long rb_min = getenv("ROD_DW_RBMIN") ? atol(getenv("ROD_DW_RBMIN")) : 16;
-  const long want = std::max<long>(1, cdivl(want_blocks, base));
-  t.RB = (int)std::min<long>(64, std::max<long>(rb_min, cdivl(Ho, want)));
+  constexpr long DW_WANT_BLOCKS = 1024;  // target blocks per launch
+  constexpr long DW_RB_MIN = 16;         // minimum output rows per block
+  const long want = std::max<long>(1, cdivl(DW_WANT_BLOCKS, base));
+  t.RB = (int)std::min<long>(64, std::max<long>(DW_RB_MIN, cdivl(Ho, want)));
   t.strips = cdiv(Ho, t.RB);
   return t;
 }
@@ -131,15 +130,12 @@ __device__ __forceinline__ void xcd_block(int& bx, int& by, int& bz) {
 // channel pack of the forward LX kernel: 16-byte packs, or (bf16) 8-byte packs with half the
 // per-thread weights / accumulators / statistics in registers (106 instead of 192 VGPRs with the
 // prologue and statistics: 4 waves / SIMD instead of 2).  tools/dw_bench.py fwdpro, per shape
-// with ROD_DW_FWD_V=4 / 8 (round 4): 8 bytes on the narrow or small maps — 720x1280x32 s1 229.6
+// with 4 / 8 channels forced (round 4): 8 bytes on the narrow or small maps — 720x1280x32 s1 229.6
 // vs 258.3 us, 180x320x192 s1 104 vs 113, 90x160x384 52 vs 62, 45x80x576 30 vs 39 — and 16
 // bytes on the wide large ones — 720x1280x96 s2 387 vs 420, 360x640x144 s1 306 vs 341,
 // 360x640x144 s2 187 vs 206.  So 16 bytes when C >= 96 and the INPUT map has > 1M pixels.
-// ROD_DW_FWD_V=4 / 8 forces one width (A/B switch).
 inline int dw_fwd_v(int dtype, long in_pixels, int C) {
-  static const int env = getenv("ROD_DW_FWD_V") ? atoi(getenv("ROD_DW_FWD_V")) : 0;
   if (dtype == ROD_F32) return 4;
-  if (env == 4 || env == 8) return env;
   return C >= 96 && in_pixels > 1024L * 1024 ? 8 : 4;
 }
 

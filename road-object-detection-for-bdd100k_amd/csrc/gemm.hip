@@ -304,12 +304,12 @@ __device__ __forceinline__ void mma32(f32x4& acc, const float* a, const float* b
 // forward: y[m, co] = sum_k A[m,k] wt[co,k] + bias[co]
 // block 256 threads = 4 waves laid out WM x WN; tile BM x BN; wave tile (BM/WM) x (BN/WN)
 // =====================================================================================
-// BKT: k depth per LDS step.  32: one LDS buffer, two barriers per step (the next step's
-// global loads in flight under the MFMAs).  64 (bf16): two LDS buffers, ONE barrier per step,
-// twice the MFMAs per wave between barriers — the deep-K 3x3 convs (K = 9 x 128), which at 32
-// were load-latency bound (a k step's MFMAs per SIMD shorter than the im2col gather latency).
+// k depth per LDS step: BK = 32, one LDS buffer, two barriers per step (the next step's global
+// loads in flight under the MFMAs).  A 64-deep double-buffered step (bf16, one barrier per step)
+// for the heads' 128 -> 128 3x3 was measured and lost: no faster at b = 8 (87.5 vs 87.1 us) and
+// slower at b = 32 (217 vs 185 us per call), 184 VGPRs and 74 KB of LDS leaving 2 waves per SIMD.
 template <typename T, int KS, int BN, bool VA, bool VB, bool VY, bool SPLIT = false, bool STATS = false,
-          bool PRO = false, bool GRED = false, int BKT = BK, bool EPI = false, bool BWD = false>
+          bool PRO = false, bool GRED = false, bool EPI = false, bool BWD = false>
 __global__ void __launch_bounds__(256) conv_fwd_kernel(const T* __restrict__ X, const T* __restrict__ Wt,
                                                        const float* __restrict__ bias, T* __restrict__ Y, long M,
                                                        int H, int W, int Cin, int Cout, int ldx, int ldy,
@@ -317,30 +317,28 @@ __global__ void __launch_bounds__(256) conv_fwd_kernel(const T* __restrict__ X, 
                                                        BnPro pro = BnPro{}, BnGred gr = BnGred{},
                                                        BnEpi ep = BnEpi{}, BnBwd bw = BnBwd{}) {
   static_assert(!EPI || (!SPLIT && !STATS && !GRED), "the BatchNorm-apply epilogue is inference-only");
-  static_assert(!BWD || (KS == 1 && VA && !PRO && !STATS && !GRED && !EPI && BKT == BK && sizeof(T) == 2),
+  static_assert(!BWD || (KS == 1 && VA && !PRO && !STATS && !GRED && !EPI && sizeof(T) == 2),
                 "the BatchNorm-backward prologue: bf16 1x1 backward-data only");
   constexpr int BM = 128;
   constexpr int WN = BN >= 64 ? 2 : 1;
   constexpr int WM = 4 / WN;
   constexpr int MT = BM / WM / 16;
   constexpr int NT = BN / WN / 16;
-  static_assert(BKT == BK || (BKT == 64 && sizeof(T) == 2 && !SPLIT), "BKT 64: bf16, no split-K");
-  constexpr bool DB = BKT == 64;                  // double-buffered LDS
-  constexpr int CPR = BKT / 8;                    // 16-byte k chunks per tile row
+  constexpr int CPR = BK / 8;                     // 16-byte k chunks per tile row
   constexpr int RPP = 256 / CPR;                  // tile rows per pass of the block
-  constexpr int LD = BKT + LdsPad<T>::v;
-  constexpr int ACH = BM * BKT / 8 / 256;          // A chunks per thread (2, or 4 at BKT 64)
-  constexpr int BCH = (BN * BKT / 8 + 255) / 256;  // B chunks per thread
+  constexpr int LD = BK + LdsPad<T>::v;
+  constexpr int ACH = BM * BK / 8 / 256;           // A chunks per thread (2)
+  constexpr int BCH = (BN * BK / 8 + 255) / 256;   // B chunks per thread
   // epilogue staging: one 64-row half of the tile at a time, row pad keeps 16-byte alignment
   constexpr int EV = 16 / sizeof(T);
   constexpr int LDC = BN + EV;
-  constexpr int MAIN_BYTES = (DB ? 2 : 1) * (BM + BN) * LD * sizeof(T);
+  constexpr int MAIN_BYTES = (BM + BN) * LD * sizeof(T);
   constexpr int EPI_BYTES = VY ? 64 * LDC * sizeof(T) : 0;
   constexpr int ST_BYTES = 0;
   constexpr int SM1 = MAIN_BYTES > EPI_BYTES ? MAIN_BYTES : EPI_BYTES;
   constexpr int SMEM = SM1 > ST_BYTES ? SM1 : ST_BYTES;
   __shared__ __attribute__((aligned(16))) char smem[SMEM];
-  T* As = (T*)smem;  // LDS buffer b: A tile at As + b(BM+BN)LD, B tile after it
+  T* As = (T*)smem;  // A tile, B tile after it
 
   const int K = KS * KS * Cin;
   const int tid = threadIdx.x;
@@ -382,7 +380,7 @@ __global__ void __launch_bounds__(256) conv_fwd_kernel(const T* __restrict__ X, 
 
   Chunk8<T> ra[ACH], rb[BCH];
   Chunk8<T> ryb[BWD ? ACH : 1];   // BWD: the y chunks beside the dz chunks in ra
-  // 3x3 with 16-byte A chunks: the k loop is sequential (k0 = kb, kb + BKT, ...), so the rows
+  // 3x3 with 16-byte A chunks: the k loop is sequential (k0 = kb, kb + BK, ...), so the rows
   // walk their taps incrementally (RowSrc::walk_*); the state always matches the chunk held in ra
   constexpr bool WALK = KS == 3 && VA;
   bool first = true;
@@ -391,7 +389,7 @@ __global__ void __launch_bounds__(256) conv_fwd_kernel(const T* __restrict__ X, 
 #pragma unroll
       for (int i = 0; i < ACH; ++i) {
         if (first) rows[i].walk_init(k0 + kc, Cin, H, W, ldx);
-        else rows[i].walk_next(BKT, Cin, H, W, ldx);
+        else rows[i].walk_next(BK, Cin, H, W, ldx);
         rows[i].walk_load(ra[i]);
       }
       first = false;
@@ -413,7 +411,7 @@ __global__ void __launch_bounds__(256) conv_fwd_kernel(const T* __restrict__ X, 
       const int r = cid / CPR;
       const int co = n0 + r;
       const int k = k0 + kc;
-      if (cid >= BN * BKT / 8) continue;
+      if (cid >= BN * BK / 8) continue;
       if (co >= Cout || k >= K) {
         rb[i].zero();
       } else if (VB && k + 8 <= K) {
@@ -440,9 +438,9 @@ __global__ void __launch_bounds__(256) conv_fwd_kernel(const T* __restrict__ X, 
   // split-K: this workgroup reduces k in [kb, ke) only
   const int kb = SPLIT ? blockIdx.z * kper : 0;
   const int ke = SPLIT ? (kb + kper < K ? kb + kper : K) : K;
-  // stage the registers of the k step at k0 into LDS buffer `buf`
-  auto store_tiles = [&](int k0, int buf) {
-    T* as = As + buf * (BM + BN) * LD;
+  // stage the registers of the k step at k0 into LDS
+  auto store_tiles = [&](int k0) {
+    T* as = As;
     T* bs = as + BM * LD;
 #pragma unroll
     for (int i = 0; i < ACH; ++i) {
@@ -468,15 +466,15 @@ __global__ void __launch_bounds__(256) conv_fwd_kernel(const T* __restrict__ X, 
 #pragma unroll
     for (int i = 0; i < BCH; ++i) {
       const int cid = tid + i * 256;
-      if (cid < BN * BKT / 8) rb[i].store_lds(bs + (cid / CPR) * LD + kc);
+      if (cid < BN * BK / 8) rb[i].store_lds(bs + (cid / CPR) * LD + kc);
     }
   };
-  auto mma_step = [&](int buf) {
-    const T* as = As + buf * (BM + BN) * LD;
+  auto mma_step = [&]() {
+    const T* as = As;
     const T* bs = as + BM * LD;
     const int fr = lane & 15, fk = (lane >> 4) * 8;
 #pragma unroll
-    for (int kk = 0; kk < BKT; kk += 32)
+    for (int kk = 0; kk < BK; kk += 32)
 #pragma unroll
       for (int a = 0; a < MT; ++a) {
         const T* pa = as + (wm * (BM / WM) + a * 16 + fr) * LD + kk + fk;
@@ -488,27 +486,12 @@ __global__ void __launch_bounds__(256) conv_fwd_kernel(const T* __restrict__ X, 
       }
   };
   load_tiles(kb);
-  if constexpr (DB) {
-    // buffer b is read in step i and rewritten in step i+1 (after that step's barrier)
-    store_tiles(kb, 0);
+  for (int k0 = kb; k0 < ke; k0 += BK) {
     __syncthreads();
-    int buf = 0;
-    for (int k0 = kb; k0 < ke; k0 += BKT) {
-      const bool more = k0 + BKT < ke;
-      if (more) load_tiles(k0 + BKT);  // next step's global loads in flight under the MFMAs
-      mma_step(buf);
-      if (more) store_tiles(k0 + BKT, buf ^ 1);
-      __syncthreads();
-      buf ^= 1;
-    }
-  } else {
-    for (int k0 = kb; k0 < ke; k0 += BKT) {
-      __syncthreads();
-      store_tiles(k0, 0);
-      __syncthreads();
-      if (k0 + BKT < ke) load_tiles(k0 + BKT);  // next tile in flight under the MFMAs
-      mma_step(0);
-    }
+    store_tiles(k0);
+    __syncthreads();
+    if (k0 + BK < ke) load_tiles(k0 + BK);  // next tile in flight under the MFMAs
+    mma_step();
   }
 
   if constexpr (SPLIT) {
@@ -1094,12 +1077,10 @@ __global__ void __launch_bounds__(256, (PRO && KT >= 5) ? 4 : (MODE == 3 ? 5 : 1
 // rod_conv_fwd's streaming path (pw_stream_kernel): bf16 1x1, no bias / prologue, K <= 96
 // (K % 8 == 0), Cout a multiple of 96, 144 or 192 (N groups of 6, 9 or 12 MFMA tiles),
 // 16-byte aligned rows, M >= 65536; statistics parts or the gred sums (dense y) or neither.
-// ROD_PW_STREAM=0 turns it off (A/B measurement switch).
 static int pw_stream_groups(long M, int K, int Cout, int& nt, bool gred = false) {
-  static const bool off = getenv("ROD_PW_STREAM") && atoi(getenv("ROD_PW_STREAM")) == 0;
   // >= 512 row tiles: on the 45x80 maps (225 tiles) the tiled kernel measured faster
   // (tools/conv_bench.py: 96->576 18.2 vs 23.1 us)
-  if (off || K > 96 || K % 8 || Cout % 16 || M < 65536) return 0;
+  if (K > 96 || K % 8 || Cout % 16 || M < 65536) return 0;
   // gred: narrow groups (3 MFMA tiles: the lane's fixed chunks span more rows, fewer VGPRs for
   // its BatchNorm constants, row sums and prefetched gr.y); otherwise the widest that divides Cout
   static const int gred_first[] = {3, 2, 4, 6, 9, 12, 8};
@@ -1972,12 +1953,11 @@ static WgradPlan wgrad_plan(long M, int Cin, int Cout, int ks) {
   p.ctiles = cdiv(Cout, WG_T);
   p.ktiles = cdiv(K, WG_T);
   const int tiles = p.ctiles * p.ktiles;
-  // measurement switches: ROD_WG_TARGET (blocks, 2048), ROD_WG_MINROWS (rows per split, 128:
-  // the heads' small-map 3x3 convs walk 2 row steps per block instead of 8; bench 384.6 (512)
-  // -> 386.9 img/s, 64 rows 386.1)
-  static const long wg_target = getenv("ROD_WG_TARGET") ? atol(getenv("ROD_WG_TARGET")) : 2048;
-  static const long wg_minrows = getenv("ROD_WG_MINROWS") ? atol(getenv("ROD_WG_MINROWS")) : 128;
-  long splits = std::max<long>(1, std::min<long>(cdivl(wg_target, tiles), cdivl(M, wg_minrows)));
+  constexpr long WG_TARGET = 2048;   // target blocks
+  // rows per split: at 128 the heads' small-map 3x3 convs walk 2 row steps per block instead of
+  // 8; bench 384.6 (512 rows) -> 386.9 img/s, 64 rows 386.1
+  constexpr long WG_MINROWS = 128;
+  long splits = std::max<long>(1, std::min<long>(cdivl(WG_TARGET, tiles), cdivl(M, WG_MINROWS)));
   long chunk = cdivl(M, splits);
   chunk = cdivl(chunk, BK) * BK;
   p.chunk = chunk;
@@ -1995,24 +1975,24 @@ static bool aligned16(const void* p) {
 
 // `pro` (nullable): BatchNorm-apply prologue on the A operand; its table takes 8*Cin bytes of
 // dynamic LDS.
-template <typename T, int KS, int BN, bool VA, bool VB, bool VY, bool PRO, int BKT = BK>
+template <typename T, int KS, int BN, bool VA, bool VB, bool VY, bool PRO>
 static void conv_fwd_launch(const void* x, const void* wt, const float* bias, void* y, long M, int H, int W, int Cin,
                             int Cout, int ldx, int ldy, float* stats, const BnPro& pro, const BnGred* gr,
                             hipStream_t s, const BnEpi* ep = nullptr, const BnBwd* bw = nullptr) {
   dim3 grid(cdivl(M, 128), cdiv(Cout, BN));
   if (grid.y > 1) grid.x = (grid.x + 7) / 8 * 8;  // XCD-aware N-tile order (see the kernel)
   const size_t lds = PRO ? 8 * (size_t)Cin : 0;
-  if constexpr (sizeof(T) == 2 && BKT == BK && KS == 1 && !PRO && VA) {   // the backward-data BatchNorm prologue
+  if constexpr (sizeof(T) == 2 && KS == 1 && !PRO && VA) {   // the backward-data BatchNorm prologue
     if (bw) {
-      hipLaunchKernelGGL((conv_fwd_kernel<T, KS, BN, VA, VB, VY, false, false, false, false, BKT, false, true>), grid,
+      hipLaunchKernelGGL((conv_fwd_kernel<T, KS, BN, VA, VB, VY, false, false, false, false, false, true>), grid,
                          dim3(256), (size_t)Cin * BWD_CF * sizeof(float), s, (const T*)x, (const T*)wt, bias, (T*)y, M,
                          H, W, Cin, Cout, ldx, ldy, nullptr, 0, pro, BnGred{}, BnEpi{}, *bw);
       return;
     }
   }
-  if constexpr (sizeof(T) == 2 && BKT == BK) {   // the inference BatchNorm-apply epilogue (bf16)
+  if constexpr (sizeof(T) == 2) {   // the inference BatchNorm-apply epilogue (bf16)
     if (ep) {
-      hipLaunchKernelGGL((conv_fwd_kernel<T, KS, BN, VA, VB, VY, false, false, PRO, false, BKT, true>), grid,
+      hipLaunchKernelGGL((conv_fwd_kernel<T, KS, BN, VA, VB, VY, false, false, PRO, false, true>), grid,
                          dim3(256), lds, s, (const T*)x, (const T*)wt, bias, (T*)y, M, H, W, Cin, Cout, ldx, ldy,
                          nullptr, 0, pro, BnGred{}, *ep);
       return;
@@ -2020,30 +2000,18 @@ static void conv_fwd_launch(const void* x, const void* wt, const float* bias, vo
   }
   if constexpr (VY) {
     if (gr) {
-      hipLaunchKernelGGL((conv_fwd_kernel<T, KS, BN, VA, VB, VY, false, false, PRO, true, BKT>), grid, dim3(256), lds, s,
+      hipLaunchKernelGGL((conv_fwd_kernel<T, KS, BN, VA, VB, VY, false, false, PRO, true>), grid, dim3(256), lds, s,
                          (const T*)x, (const T*)wt, bias, (T*)y, M, H, W, Cin, Cout, ldx, ldy, nullptr, 0, pro, *gr);
       return;
     }
     if (stats) {
-      hipLaunchKernelGGL((conv_fwd_kernel<T, KS, BN, VA, VB, VY, false, true, PRO, false, BKT>), grid, dim3(256), lds, s,
+      hipLaunchKernelGGL((conv_fwd_kernel<T, KS, BN, VA, VB, VY, false, true, PRO, false>), grid, dim3(256), lds, s,
                          (const T*)x, (const T*)wt, bias, (T*)y, M, H, W, Cin, Cout, ldx, ldy, stats, 0, pro);
       return;
     }
   }
-  hipLaunchKernelGGL((conv_fwd_kernel<T, KS, BN, VA, VB, VY, false, false, PRO, false, BKT>), grid, dim3(256), lds, s,
+  hipLaunchKernelGGL((conv_fwd_kernel<T, KS, BN, VA, VB, VY, false, false, PRO, false>), grid, dim3(256), lds, s,
                      (const T*)x, (const T*)wt, bias, (T*)y, M, H, W, Cin, Cout, ldx, ldy, nullptr, 0, pro);
-}
-
-// k depth 64 with double-buffered LDS (bf16) for the 3x3 convs with K % 64 == 0 and a 97..128-wide
-// N tile (the heads' 128 -> 128 3x3), ROD_GEMM_BK64=1 (2: also the 1x1 convs with K >= 256).  Off
-// by default: measured no faster at b = 8 (87.5 vs 87.1 us) and slower at b = 32 (217 vs 185 us per
-// call): 184 VGPRs and 74 KB of LDS drop the kernel from 3 to 2 waves per SIMD.
-static int bk64_mode() {
-  static const int m = [] {
-    const char* e = getenv("ROD_GEMM_BK64");
-    return e ? atoi(e) : 0;
-  }();
-  return m;
 }
 
 // N tile: the whole of Cout in one tile up to 256 (A is read once), else 128-wide tiles.
@@ -2061,15 +2029,6 @@ static void conv_fwd_dispatch(bool va, bool vb, bool vy, const void* x, const vo
                                                     bw);
   };
   if (va && vb && vy) {
-    if constexpr (sizeof(T) == 2) {
-      const int K = KS * KS * Cin;
-      const int mode = bk64_mode();
-      if (!ep && !bw && mode > 0 && K % 64 == 0 && Cout > 96 && Cout <= 128 && (KS == 3 || (mode > 1 && K >= 256))) {
-        conv_fwd_launch<T, KS, 128, true, true, true, PRO, 64>(x, wt, bias, y, M, H, W, Cin, Cout, ldx, ldy, stats,
-                                                                pro, gr, s);
-        return;
-      }
-    }
     const int bn = Cout <= 192 ? cdiv(Cout, 32) * 32 : Cout <= 256 ? 256 : 128;
     sel_int<32, 64, 96, 128, 160, 192, 256>(bn, [&](auto BN_) { cf(BN_, std::true_type{}, std::true_type{}); });
     return;
@@ -2091,7 +2050,7 @@ static void conv_fwd_split_t(const SplitPlan& p, const void* x, const void* wt, 
   const size_t lds = PRO ? 8 * (size_t)Cin : 0;
   if constexpr (sizeof(T) == 2 && KS == 1 && !PRO && VA) {
     if (bw) {
-      hipLaunchKernelGGL((conv_fwd_kernel<T, KS, 128, VA, VB, false, true, false, false, false, BK, false, true>), grid,
+      hipLaunchKernelGGL((conv_fwd_kernel<T, KS, 128, VA, VB, false, true, false, false, false, false, true>), grid,
                          dim3(256), (size_t)Cin * BWD_CF * sizeof(float), s, (const T*)x, (const T*)wt, nullptr,
                          nullptr, M, H, W, Cin, Cout, ldx, 0, part, p.kper, pro, BnGred{}, BnEpi{}, *bw);
       return;
@@ -2127,9 +2086,8 @@ static void conv_fwd_typed(const void* x, const BnPro* pro, const void* wt, cons
   const int nparts = (int)cdivl(M, 128);
   const int dt = sizeof(T) == 4 ? ROD_F32 : ROD_BF16;
   const BnPro pv = pro ? *pro : BnPro{};
-  static const bool old_stem_fwd = getenv("ROD_DEBUG_OLDSTEMFWD") != nullptr;  // A/B against the VALU kernel
   if constexpr (sizeof(T) == 2) {
-    if (!pro && !gr && !ep && !bw && ksize == 3 && Cin == 3 && Cout == 32 && vy && !old_stem_fwd) {
+    if (!pro && !gr && !ep && !bw && ksize == 3 && Cin == 3 && Cout == 32 && vy) {
       const bool fuse = stats != nullptr && W % SW_TW == 0;  // block == stat tile
       // rows per block: >= ~4 blocks' worth per CU of rows, pipelined within a block
       const int xb = cdiv(W, SW_TW);
@@ -2170,15 +2128,20 @@ static void conv_fwd_typed(const void* x, const BnPro* pro, const void* wt, cons
     if (gr) gred_parts(dt, y, gr->y, gr->p, M, Cout, gr->parts, nparts, s);
     return;
   }
-  static const bool no_stem = getenv("ROD_DEBUG_NOSTEM") != nullptr;  // debug bisection
-  if (!pro && !gr && !ep && ksize == 3 && Cin == 3 && (Cout == 32 || Cout == 64) && vy && !no_stem) {
-    if (Cout == 32)
-      hipLaunchKernelGGL((stem_conv_fwd_kernel<T, 32>), dim3(cdiv(W, 128), H, N), dim3(256), 0, s, (const T*)x,
-                         (const T*)wt, bias, (T*)y, H, W, ldx, ldy);
-    else
+  // the VALU stem kernel: fp32 3 -> 32 (bf16 took the MFMA kernel above) and 3 -> 64 (VGG)
+  if (!pro && !gr && !ep && ksize == 3 && Cin == 3 && vy) {
+    if constexpr (sizeof(T) == 4) {
+      if (Cout == 32) {
+        hipLaunchKernelGGL((stem_conv_fwd_kernel<T, 32>), dim3(cdiv(W, 128), H, N), dim3(256), 0, s, (const T*)x,
+                           (const T*)wt, bias, (T*)y, H, W, ldx, ldy);
+        return;
+      }
+    }
+    if (Cout == 64) {
       hipLaunchKernelGGL((stem_conv_fwd_kernel<T, 64>), dim3(cdiv(W, 64), H, N), dim3(256), 0, s, (const T*)x,
                          (const T*)wt, bias, (T*)y, H, W, ldx, ldy);
-    return;
+      return;
+    }
   }
   if constexpr (sizeof(T) == 2) {
     if (!ep && !bw && !gr && pro && ksize == 1 && !bias && va && vb && vy && Cin <= PRO_MAXC &&
@@ -2240,10 +2203,9 @@ static void wgrad_typed(const void* x, const BnPro* pro, const void* dy, float* 
   const bool va = aligned16<T>(x) && (ldx % eV == 0) && (ksize == 1 ? true : (Cin % 8 == 0));
   const bool vd = aligned16<T>(dy) && (lddy % eV == 0);
   const BnPro pv = pro ? *pro : BnPro{};
-  static const bool old_stem = getenv("ROD_DEBUG_OLDSTEMWG") != nullptr;  // A/B against the generic kernel
   bool stem = false;
   if constexpr (sizeof(T) == 2) {
-    if (!pro && ksize == 3 && Cin == 3 && Cout == 32 && vd && !old_stem) {
+    if (!pro && ksize == 3 && Cin == 3 && Cout == 32 && vd) {
       const StemWgradPlan sp = stem_wgrad_plan(N, H, W);
       hipLaunchKernelGGL(stem_wgrad_kernel<false>, dim3(sp.xb, sp.yb, N), dim3(256), 0, s, (const bf16_t*)x,
                          (const bf16_t*)dy, part, H, W, ldx, lddy, sp.rb, StemBnb{});
@@ -2307,9 +2269,12 @@ int rod_conv_fwd(const void* x, const float* pro_mean, const float* pro_rstd, co
                 "rod_conv_fwd: gred needs y, mean, rstd, a dense output and no stat_parts");
   const BnPro pro{pro_mean, pro_rstd, pro_gamma, pro_beta, pro_act};
   const BnGred gr{gred_y, BnPro{gred_mean, gred_rstd, gred_gamma, gred_beta, gred_act}, gred_parts};
-  ROD_DISPATCH_DTYPE(dtype, conv_fwd_typed<T>(x, pro_mean ? &pro : nullptr, wt, bias, y, workspace, stat_parts,
-                                              gred_parts ? &gr : nullptr, N, H, W, Cin, Cout, ksize, ldx, ldy,
-                                              ROD_STREAM(stream)));
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
+    conv_fwd_typed<T>(x, pro_mean ? &pro : nullptr, wt, bias, y, workspace, stat_parts, gred_parts ? &gr : nullptr, N,
+                      H, W, Cin, Cout, ksize, ldx, ldy, ROD_STREAM(stream));
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_conv_fwd: unsupported dtype code %d", dtype);
   return check_launch("rod_conv_fwd");
 }
 
@@ -2400,16 +2365,24 @@ int rod_conv_weight_prep(const float* w, void* wt, int Cout, int Cin, int ksize,
   ROD_CHECK_ARG(Cout > 0 && Cin > 0 && (ksize == 1 || ksize == 3), "rod_conv_weight_prep: bad shape");
   ROD_CHECK_ARG(mode == 0 || mode == 1, "rod_conv_weight_prep: bad mode %d", mode);
   const long n = (long)Cout * ksize * ksize * Cin;
-  ROD_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(weight_prep_kernel<T>, dim3(cdivl(n, 256)), dim3(256), 0,
-                                               ROD_STREAM(stream), w, (T*)wt, Cout, Cin, ksize, mode));
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
+    hipLaunchKernelGGL(weight_prep_kernel<T>, dim3(cdivl(n, 256)), dim3(256), 0, ROD_STREAM(stream), w, (T*)wt, Cout,
+                       Cin, ksize, mode);
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_conv_weight_prep: unsupported dtype code %d", dtype);
   return check_launch("rod_conv_weight_prep");
 }
 
 int rod_conv_weight_prep_batch(const void* table, int n, long total, int dtype, void* stream) {
   ROD_CHECK_ARG(table != nullptr && n > 0 && total > 0, "rod_conv_weight_prep_batch: bad arguments");
   const int blocks = (int)std::min<long>(cdivl(total, 256), 4096);
-  ROD_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(weight_prep_batch_kernel<T>, dim3(blocks), dim3(256), 0,
-                                               ROD_STREAM(stream), (const PrepEntry*)table, n, total));
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
+    hipLaunchKernelGGL(weight_prep_batch_kernel<T>, dim3(blocks), dim3(256), 0, ROD_STREAM(stream),
+                       (const PrepEntry*)table, n, total);
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_conv_weight_prep_batch: unsupported dtype code %d", dtype);
   return check_launch("rod_conv_weight_prep_batch");
 }
 
@@ -2431,8 +2404,12 @@ int rod_conv_wgrad(const void* x, const float* pro_mean, const float* pro_rstd, 
   ROD_CHECK_ARG(ldx >= Cin && lddy >= Cout, "rod_conv_wgrad: leading dim too small");
   ROD_CHECK_ARG(!pro_mean || (pro_rstd && Cin <= PRO_MAXC), "rod_conv_wgrad: bad BatchNorm prologue (Cin %d)", Cin);
   const BnPro pro{pro_mean, pro_rstd, pro_gamma, pro_beta, pro_act};
-  ROD_DISPATCH_DTYPE(dtype, wgrad_typed<T>(x, pro_mean ? &pro : nullptr, dy, dw, db, (float*)workspace, N, H, W, Cin,
-                                           Cout, ksize, ldx, lddy, ROD_STREAM(stream)));
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
+    wgrad_typed<T>(x, pro_mean ? &pro : nullptr, dy, dw, db, (float*)workspace, N, H, W, Cin, Cout, ksize, ldx, lddy,
+                   ROD_STREAM(stream));
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_conv_wgrad: unsupported dtype code %d", dtype);
   return check_launch("rod_conv_wgrad");
 }
 

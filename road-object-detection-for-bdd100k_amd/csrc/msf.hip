@@ -247,7 +247,8 @@ int rod_pad2d(const void* x, void* y, int N, int H, int W, int C, int top, int l
                     Wp >= W + left,
                 "rod_pad2d: bad arguments");
   hipStream_t s = ROD_STREAM(stream);
-  ROD_DISPATCH_DTYPE(dtype, {
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
     const bool vec = C % Vec16<T>::N == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0;
     const int V = vec ? Vec16<T>::N : 1;
     // inverse: [N, Hp, Wp] -> [N, H, W] (read shifted by +top / +left)
@@ -260,7 +261,8 @@ int rod_pad2d(const void* x, void* y, int N, int H, int W, int C, int top, int l
     else
       hipLaunchKernelGGL((pad2d_kernel<T, false>), dim3(g), dim3(256), 0, s, (const T*)x, (T*)y, N, Hy, Wy, Hx, Wx,
                          C, dh, dw);
-  });
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_pad2d: unsupported dtype code %d", dtype);
   return check_launch("rod_pad2d");
 }
 
@@ -269,10 +271,11 @@ int rod_space_to_depth(const void* x, void* y, int N, int H, int W, int C, int b
   ROD_CHECK_ARG(x && y && N > 0 && C > 0 && block >= 2 && H % block == 0 && W % block == 0,
                 "rod_space_to_depth: bad arguments (H, W must be multiples of the block)");
   hipStream_t s = ROD_STREAM(stream);
-  ROD_DISPATCH_DTYPE(dtype, {
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
     const bool vec = C % Vec16<T>::N == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0;
     const unsigned g = g256((long)N * H * W * (C / (vec ? Vec16<T>::N : 1)));
-if (vec && inverse)
+    if (vec && inverse)
       hipLaunchKernelGGL((s2d_kernel<T, true, true>), dim3(g), dim3(256), 0, s, (const T*)x, (T*)y, N, H, W, C, block);
     else if (vec)
       hipLaunchKernelGGL((s2d_kernel<T, true, false>), dim3(g), dim3(256), 0, s, (const T*)x, (T*)y, N, H, W, C, block);
@@ -281,7 +284,8 @@ if (vec && inverse)
     else
       hipLaunchKernelGGL((s2d_kernel<T, false, false>), dim3(g), dim3(256), 0, s, (const T*)x, (T*)y, N, H, W, C,
                          block);
-  });
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_space_to_depth: unsupported dtype code %d", dtype);
   return check_launch("rod_space_to_depth");
 }
 
@@ -292,14 +296,16 @@ int rod_se_fwd(const void* x, const float* w1, const float* b1, const float* w2,
   const int V = dtype == ROD_F32 ? 4 : 8;
   ROD_CHECK_ARG(C % V == 0 && (size_t)(C + C8) * 4 <= 64 * 1024, "rod_se_fwd: C=%d unsupported", C);
   hipStream_t s = ROD_STREAM(stream);
-  ROD_DISPATCH_DTYPE(dtype, {
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
     hipLaunchKernelGGL((se_rowsum_kernel<T, false>), dim3(cdiv(C / V, 16), N), dim3(256), 0, s, (const T*)x,
                        (const T*)nullptr, sq, HW, C, (float)(1.0 / (double)HW));
     hipLaunchKernelGGL(se_excite_kernel, dim3(N), dim3(256), (C + C8) * sizeof(float), s, sq, w1, b1, w2, b2, hid, e,
                        C, C8);
     hipLaunchKernelGGL((se_scale_kernel<T>), dim3(g256((long)N * HW * C)), dim3(256), 0, s, (const T*)x, e, (T*)y,
                        HW, C, (long)N * HW * C);
-  });
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_se_fwd: unsupported dtype code %d", dtype);
   return check_launch("rod_se_fwd");
 }
 
@@ -311,14 +317,16 @@ int rod_se_bwd(const void* dy, const void* x, const float* w1, const float* w2, 
   const int V = dtype == ROD_F32 ? 4 : 8;
   ROD_CHECK_ARG(C % V == 0 && (size_t)N * (C + C8) * 4 <= 64 * 1024, "rod_se_bwd: N=%d C=%d unsupported", N, C);
   hipStream_t s = ROD_STREAM(stream);
-  ROD_DISPATCH_DTYPE(dtype, {
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
     hipLaunchKernelGGL((se_rowsum_kernel<T, true>), dim3(cdiv(C / V, 16), N), dim3(256), 0, s, (const T*)dy,
                        (const T*)x, de, HW, C, 1.f);
     hipLaunchKernelGGL(se_excite_bwd_kernel, dim3(1), dim3(256), (size_t)N * (C + C8) * sizeof(float), s, de, sq,
                        w1, w2, hid, e, dsq, dw1, db1, dw2, db2, N, C, C8);
     hipLaunchKernelGGL((se_input_grad_kernel<T>), dim3(g256((long)N * HW * C)), dim3(256), 0, s, (const T*)dy, e,
                        dsq, (T*)dx, HW, C, (long)N * HW * C);
-  });
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_se_bwd: unsupported dtype code %d", dtype);
   return check_launch("rod_se_bwd");
 }
 

@@ -978,16 +978,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) p
   }
 }
 
-// the group width of the gred form for (Cin, Cout); 0: not taken (ROD_PWB_GRED=0: never)
+// the group width of the gred form for (Cin, Cout); 0: not taken
 static int pw_bwd_gred_nw(int Cin, int Cout) {
-  static const bool off = getenv("ROD_PWB_GRED") && atoi(getenv("ROD_PWB_GRED")) == 0;
-  if (off || !(Cout == 16 || Cout == 24 || Cout == 32 || Cout == 64)) return 0;
+  if (!(Cout == 16 || Cout == 24 || Cout == 32 || Cout == 64)) return 0;
   // Cout 64 at 48 columns spills under the 3-waves/SIMD bound (168 VGPRs); 32 columns fit (162)
   if (Cout == 64) return Cin % 32 == 0 ? 32 : 0;
   // 32-column groups wherever Cin allows (tools/pwgred_bench.py: 96->24 289 -> 256 us, 192->32
   // 139 -> 121 us against 48: no idle row group, 4 waves / SIMD), 48 for Cin = 144
-  static const int force = getenv("ROD_PWB_GRED_NW") ? atoi(getenv("ROD_PWB_GRED_NW")) : 0;   // A/B switch
-  if (force == 48 && Cin % 48 == 0) return 48;
   if (Cin % 32 == 0) return 32;
   if (Cin % 48 == 0) return 48;
   return 0;
@@ -1005,11 +1002,10 @@ struct PwBwdPlan {
   size_t lds;
 };
 
-// the streaming kernel's shapes (expand convs without bias); ROD_PWB_STREAM=0 turns it off
+// the streaming kernel's shapes (expand convs without bias)
 static bool pw_bwd_stream_ok(int Cin, int Cout, bool bias) {
-  static const bool off = getenv("ROD_PWB_STREAM") && atoi(getenv("ROD_PWB_STREAM")) == 0;
   // 32->192 stays on the block kernel: 248 VGPRs (2 waves / SIMD), measured slower (168 vs 152 us)
-  return !off && !bias && ((Cin == 16 && Cout == 96) || (Cin == 24 && Cout == 144));
+  return !bias && ((Cin == 16 && Cout == 96) || (Cin == 24 && Cout == 144));
 }
 // blocks of the streaming launch: 3 per CU (the register budget of the 16->96 form), at most one
 // 4-wave group per 4 tiles
@@ -1204,18 +1200,25 @@ static int pw_bwd_gred_run(const void* dz, const void* y, const float* mean, con
               (bf16_t*)dyp};
   const long ntiles = cdivl(M, 32);
   const dim3 grid(nblk, Cin / nw);
-  // the inverted-residual block's case; at 48 columns the packed form measured slower (144->24:
-  // 569 vs 433 us), so there the per-element form runs (ROD_PWB_GRED_FAST48=1: packed, A/B)
-  static const bool fast48 = getenv("ROD_PWB_GRED_FAST48") && atoi(getenv("ROD_PWB_GRED_FAST48")) == 1;
-  const bool fast = act == ROD_ACT_NONE && xact == ROD_ACT_RELU6 && (nw == 32 || fast48);
-  // Cout 16 / 24 / 32 / 64 in groups of nw = 32 or 48 columns (pw_bwd_gred_nw; it gives Cout 64
-  // 32 only, so the <64, 48> forms are built but never selected)
+  // the inverted-residual block's case takes the packed form; at 48 columns it measured slower
+  // (144->24: 569 vs 433 us), so there the per-element form runs
+  const bool fast = act == ROD_ACT_NONE && xact == ROD_ACT_RELU6 && nw == 32;
+  // Cout 16 / 24 / 32 / 64 in groups of nw = 32 or 48 columns (pw_bwd_gred_nw); 48 columns take
+  // neither Cout 64 nor the packed form, so those are not built
   const bool hit = sel_int<16, 24, 32, 64>(Cout, [&](auto CO) {
     return sel_int<32, 48>(nw, [&](auto NW) {
-      sel_bool(fast, [&](auto F) {
-        sel_bool(dyp != nullptr, [&](auto D) {
-          launch_lds(pw_bwd_gred_kernel<CO, NW, F, D>, grid, dim3(256), PbgGeo<CO, NW>::lds(), s, a, ntiles, xparts);
-        });
+      return sel_bool(fast, [&](auto F) {
+        constexpr int co = decltype(CO)::value, nwc = decltype(NW)::value;
+        constexpr bool f = decltype(F)::value;
+        if constexpr (nwc == 48 && (co == 64 || f)) {
+          return false;
+        } else {
+          sel_bool(dyp != nullptr, [&](auto D) {
+            launch_lds(pw_bwd_gred_kernel<co, nwc, f, D>, grid, dim3(256), PbgGeo<co, nwc>::lds(), s, a, ntiles,
+                       xparts);
+          });
+          return true;
+        }
       });
     });
   });

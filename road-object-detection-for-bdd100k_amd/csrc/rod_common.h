@@ -337,18 +337,3 @@ inline void launch_lds(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hi
   } while (0)
 
 #define ROD_STREAM(s) ((hipStream_t)(s))
-
-// dispatch on storage dtype: defines `T` inside the body
-#define ROD_DISPATCH_DTYPE(dt, ...)                                   \
-  do {                                                                \
-    if ((dt) == ROD_F32) {                                            \
-      typedef float T;                                                \
-      __VA_ARGS__;                                                    \
-    } else if ((dt) == ROD_BF16) {                                    \
-      typedef bf16_t T;                                               \
-      __VA_ARGS__;                                                    \
-    } else {                                                          \
-      ::rod::set_error("unsupported dtype code %d", (int)(dt));        \
-      return ROD_EINVAL;                                              \
-    }                                                                 \
-  } while (0)

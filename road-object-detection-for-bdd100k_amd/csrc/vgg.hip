@@ -209,8 +209,12 @@ int rod_maxpool2x2(const void* x, void* y, uint8_t* argmax, int N, int H, int W,
   ROD_CHECK_ARG(C % V == 0, "rod_maxpool2x2: C %% %d != 0", V);
   const int Ho = H / 2, Wo = W / 2;
   hipStream_t s = ROD_STREAM(stream);
-  ROD_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((maxpool2x2_kernel<T>), dim3(grid1((long)N * Ho * Wo * (C / V))),
-                                               dim3(256), 0, s, (const T*)x, (T*)y, argmax, N, H, W, C, Ho, Wo));
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
+    hipLaunchKernelGGL((maxpool2x2_kernel<T>), dim3(grid1((long)N * Ho * Wo * (C / V))), dim3(256), 0, s, (const T*)x,
+                       (T*)y, argmax, N, H, W, C, Ho, Wo);
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_maxpool2x2: unsupported dtype code %d", dtype);
   return check_launch("rod_maxpool2x2");
 }
 
@@ -220,9 +224,12 @@ int rod_maxpool2x2_bwd(const void* dy, const uint8_t* argmax, void* dx, int N, i
   const int V = dtype == ROD_F32 ? 4 : 8;
   ROD_CHECK_ARG(C % V == 0, "rod_maxpool2x2_bwd: C %% %d != 0", V);
   hipStream_t s = ROD_STREAM(stream);
-  ROD_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((maxpool2x2_bwd_kernel<T>), dim3(grid1((long)N * H * W * (C / V))),
-                                               dim3(256), 0, s, (const T*)dy, argmax, (T*)dx, N, H, W, C, H / 2,
-                                               W / 2));
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
+    hipLaunchKernelGGL((maxpool2x2_bwd_kernel<T>), dim3(grid1((long)N * H * W * (C / V))), dim3(256), 0, s,
+                       (const T*)dy, argmax, (T*)dx, N, H, W, C, H / 2, W / 2);
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_maxpool2x2_bwd: unsupported dtype code %d", dtype);
   return check_launch("rod_maxpool2x2_bwd");
 }
 
@@ -230,16 +237,24 @@ int rod_dropout(const void* x, void* y, uint8_t* mask, long n, float keep_prob, 
                 void* stream) {
   ROD_CHECK_ARG(x && y && mask && n > 0 && keep_prob > 0.f && keep_prob <= 1.f, "rod_dropout: bad arguments");
   hipStream_t s = ROD_STREAM(stream);
-  ROD_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((dropout_kernel<T>), dim3(grid1(n)), dim3(256), 0, s, (const T*)x,
-                                               (T*)y, mask, n, keep_prob, seed));
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
+    hipLaunchKernelGGL((dropout_kernel<T>), dim3(grid1(n)), dim3(256), 0, s, (const T*)x, (T*)y, mask, n, keep_prob,
+                       seed);
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_dropout: unsupported dtype code %d", dtype);
   return check_launch("rod_dropout");
 }
 
 int rod_dropout_bwd(const void* dy, const uint8_t* mask, void* dx, long n, float keep_prob, int dtype, void* stream) {
   ROD_CHECK_ARG(dy && mask && dx && n > 0 && keep_prob > 0.f && keep_prob <= 1.f, "rod_dropout_bwd: bad arguments");
   hipStream_t s = ROD_STREAM(stream);
-  ROD_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((dropout_bwd_kernel<T>), dim3(grid1(n)), dim3(256), 0, s,
-                                               (const T*)dy, mask, (T*)dx, n, keep_prob));
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
+    hipLaunchKernelGGL((dropout_bwd_kernel<T>), dim3(grid1(n)), dim3(256), 0, s, (const T*)dy, mask, (T*)dx, n,
+                       keep_prob);
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_dropout_bwd: unsupported dtype code %d", dtype);
   return check_launch("rod_dropout_bwd");
 }
 
@@ -255,14 +270,16 @@ int rod_im2col3x3(const void* x, const float* pro_mean, const float* pro_rstd, c
   hipStream_t s = ROD_STREAM(stream);
   const BnPro pro{pro_mean, pro_rstd, pro_gamma, pro_beta, pro_act};
   const unsigned g = grid1((long)N * Ho * Wo * 9 * (C / V));
-  ROD_DISPATCH_DTYPE(dtype, {
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
     if (pro_mean)
       hipLaunchKernelGGL((im2col3x3_kernel<T, true>), dim3(g), dim3(256), 0, s, (const T*)x, pro, (T*)col, N, H, W,
                          C, stride, pad_t, pad_l, Ho, Wo);
     else
       hipLaunchKernelGGL((im2col3x3_kernel<T, false>), dim3(g), dim3(256), 0, s, (const T*)x, pro, (T*)col, N, H, W,
                          C, stride, pad_t, pad_l, Ho, Wo);
-  });
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_im2col3x3: unsupported dtype code %d", dtype);
   return check_launch("rod_im2col3x3");
 }
 
@@ -273,9 +290,12 @@ int rod_col2im3x3(const void* col, void* dx, int N, int H, int W, int C, int str
   const int V = dtype == ROD_F32 ? 4 : 8;
   ROD_CHECK_ARG(C % V == 0, "rod_col2im3x3: C %% %d != 0", V);
   hipStream_t s = ROD_STREAM(stream);
-  ROD_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((col2im3x3_kernel<T>), dim3(grid1((long)N * H * W * (C / V))),
-                                               dim3(256), 0, s, (const T*)col, (T*)dx, N, H, W, C, stride, pad_t,
-                                               pad_l, Ho, Wo));
+  auto run = [&](auto tag) {
+    typedef decltype(tag) T;
+    hipLaunchKernelGGL((col2im3x3_kernel<T>), dim3(grid1((long)N * H * W * (C / V))), dim3(256), 0, s, (const T*)col,
+                       (T*)dx, N, H, W, C, stride, pad_t, pad_l, Ho, Wo);
+  };
+  ROD_CHECK_ARG(sel_dtype(dtype, run), "rod_col2im3x3: unsupported dtype code %d", dtype);
   return check_launch("rod_col2im3x3");
 }
 

@@ -190,7 +190,7 @@ def test_pw_stream_expand(dev, Cin, Cout, NHW):
     """The streaming 1x1 forward (pw_stream_kernel: bf16, no bias, K <= 64, Cout % 16 == 0,
     M >= 65536; M here not a multiple of the 128-row part tile) against the oracle conv, and its
     statistics parts against the separate statistics pass (ref conv_blocks.py:264-271 expand +
-    BatchNorm).  ROD_PW_STREAM=0 would route these shapes to the tiled kernel."""
+    BatchNorm).  Shapes outside the streaming plan take the tiled kernel."""
     g = torch.Generator().manual_seed(14)
     N, H, W = NHW
     x = (torch.randn(N, H, W, Cin, generator=g) + 0.5).to(torch.bfloat16).float()

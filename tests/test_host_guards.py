@@ -9,6 +9,7 @@
   * ParamStore.eval_views serves a BatchNorm's eval slices only for buffers that really are
     views of the flat moving-statistics buffer;
   * ROD_DISABLE / ROD_ENABLE tokens the code does not read are rejected (ops._switches).
+  * the library reads two environment variables and DESIGN.md's table lists every one the project reads.
 """
 import os
 import struct
@@ -199,3 +200,30 @@ def test_switches_reject_unknown_tokens():
                 for tok, var in re.findall(r"""["'](\w+)["'] (?:not )?in (?:ops\.)?(_DISABLE|_ENABLE)\b""", src):
                     read[var].add(tok)
     assert read['_DISABLE'] == set(ops._DISABLE_KNOWN) and read['_ENABLE'] == set(ops._ENABLE_KNOWN), read
+
+
+def test_env_switches_are_documented():
+    """The library reads exactly two environment variables — ROD_PW_PROJ and ROD_MERGE_TWO_LAUNCH,
+    both per call, both with a test that runs each side in one process; every other tuning value in
+    csrc/ is a named constant — and DESIGN.md's "Run-time switches" table lists them and every
+    ROD_* variable rod/*.py and predict.py read from os.environ."""
+    import glob
+    import re
+    pkg = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(ops.__file__)), '..'))
+    csrc = os.path.join(pkg, 'csrc')
+    files = glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.h')) + \
+        glob.glob(os.path.join(csrc, 'io', '*'))
+    assert len(files) > 10, files
+    c_side = set()
+    for f in files:
+        c_side |= set(re.findall(r'getenv\(\s*"(\w+)"\s*\)', open(f).read()))
+    assert c_side == {'ROD_PW_PROJ', 'ROD_MERGE_TWO_LAUNCH'}, sorted(c_side)
+    py_side = set()
+    for f in glob.glob(os.path.join(pkg, 'rod', '*.py')) + [os.path.join(pkg, 'predict.py')]:
+        py_side |= set(re.findall(r"""environ(?:\.get\(|\[)\s*["'](ROD_\w+)["']""", open(f).read()))
+    assert {'ROD_LIB', 'ROD_DISABLE', 'ROD_ENABLE', 'ROD_HEAD_STREAMS', 'ROD_DW_FUSED_MIN'} <= py_side, sorted(py_side)
+    design = open(os.path.join(pkg, '..', 'DESIGN.md')).read()
+    m = re.search(r'^## [^\n]*Run-time switches\n(.*?)(?=^## )', design, re.S | re.M)
+    assert m, 'DESIGN.md has no "Run-time switches" section'
+    table = set(re.findall(r'^\| `(\w+)` \|', m.group(1), re.M))
+    assert c_side | py_side <= table, sorted((c_side | py_side) - table)

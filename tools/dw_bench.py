@@ -3,7 +3,7 @@ librod entries with HIP events on the launching stream and reports algorithmic G
 (rod.roofline per-unit bytes), and writes the outputs to compare kernel variants.
 
 usage: python tools/dw_bench.py [--dtype bf16|f32] [--out file.pt] [--check ref.pt] [--iters N]
-Run once per variant (e.g. ROD_DW_LEGACY=1 for the register-strip kernels)."""
+Run once per variant (e.g. per library build, through ROD_LIB)."""
 import argparse
 import os
 import sys

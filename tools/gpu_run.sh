@@ -30,44 +30,15 @@ for step in "$@"; do
     rcinf) run rcinftest 300 python -u -m pytest tests/test_gpu_recompute.py -k predict -m gpu -v --timeout 240 --timeout-method thread -p no:cacheprovider &&
          for i in 1 2; do run pinf0_$i 200 env ROD_DISABLE=rcinf python tools/predict_bench.py --res 1080 --batch 8 --iters 30 && run pinf1_$i 200 python tools/predict_bench.py --res 1080 --batch 8 --iters 30 && run pinf720_0_$i 200 env ROD_DISABLE=rcinf python tools/predict_bench.py --res 720 --batch 32 --iters 20 && run pinf720_1_$i 200 python tools/predict_bench.py --res 720 --batch 32 --iters 20; done; grep -H ms_per_batch $OUT/${TAG}_pinf*.log ;;
     rcinfab) for i in 1 2; do for cfg in "" "ROD_DISABLE=irblock" "ROD_DISABLE=irblock,rcinf1"; do n=$(echo "$cfg" | tr -c 'a-z0-9\n' '_'); run pq${n}_$i 200 env $cfg python tools/predict_bench.py --res 1080 --batch 8 --iters 30 && run pq720${n}_$i 200 env $cfg python tools/predict_bench.py --res 720 --batch 32 --iters 20; done; done; grep -H ms_per_batch $OUT/${TAG}_pq*.log ;;
-    rcfwdab) run rcfwdtest 400 python -u -m pytest tests/test_gpu_recompute.py tests/test_gpu_irblock.py -k "dw3x3_fwd_rc or predict or step or backbone" -m gpu -v --timeout 300 --timeout-method thread -p no:cacheprovider &&
-         run rcb_prev 200 env ROD_LIB=road-object-detection-for-bdd100k_amd/lib/librod_prev.so python tools/rc_bench.py b1 b2 b3 b6 && run rcb_new 200 python tools/rc_bench.py b1 b2 b3 b6 && run rcb_narrow 200 env ROD_STATS_NARROW=1 python tools/rc_bench.py b1 b3 &&
-         for i in 1 2; do run pr0_$i 200 env ROD_LIB=road-object-detection-for-bdd100k_amd/lib/librod_prev.so python tools/predict_bench.py --res 1080 --batch 8 --iters 30 && run pr1_$i 200 python tools/predict_bench.py --res 1080 --batch 8 --iters 30; done &&
-         for i in 1 2; do run tr0_$i 300 env ROD_LIB=road-object-detection-for-bdd100k_amd/lib/librod_prev.so python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run tr1_$i 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0; done;
-         grep -H "dwfwd\|expand" $OUT/${TAG}_rcb_*.log; grep -H ms_per_batch $OUT/${TAG}_pr*.log; grep -H -o '"value": [0-9.]*' $OUT/${TAG}_tr*.log ;;
-    rcv) run rcvtest 300 env ROD_DW_RC_V=4 python -u -m pytest tests/test_gpu_recompute.py -k predict -m gpu -v --timeout 240 --timeout-method thread -p no:cacheprovider &&
-         for i in 1 2; do run pv8_$i 200 python tools/predict_bench.py --res 1080 --batch 8 --iters 30 && run pv4_$i 200 env ROD_DW_RC_V=4 python tools/predict_bench.py --res 1080 --batch 8 --iters 30; done &&
-         for i in 1 2; do run qv8_$i 200 python tools/predict_bench.py --res 720 --batch 32 --iters 20 && run qv4_$i 200 env ROD_DW_RC_V=4 python tools/predict_bench.py --res 720 --batch 32 --iters 20; done;
-         grep -H ms_per_batch $OUT/${TAG}_pv*.log $OUT/${TAG}_qv*.log ;;
-    statsab) run statstest 400 python -u -m pytest tests/test_gpu_recompute.py -m gpu -v --timeout 300 --timeout-method thread -p no:cacheprovider &&
-         run stb0 200 env ROD_STATS_TILE=0 python tools/rc_bench.py b1 b3 && run stb1 200 python tools/rc_bench.py b1 b3 &&
-         for i in 1 2; do run st0_$i 300 env ROD_STATS_TILE=0 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run st1_$i 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0; done;
-         grep -H "expand" $OUT/${TAG}_stb*.log; grep -H -o '"value": [0-9.]*' $OUT/${TAG}_st?_*.log ;;
     c5heads) run cbh0 200 python tools/conv_bench.py --shapes 19,20,21,22,23 --ops fwd_plain && run cbh1 200 env ROD_DISABLE=splitk python tools/conv_bench.py --shapes 19,20,21,22,23 --ops fwd_plain ;;
     cinpad) run cptest 400 python -u -m pytest tests/test_gpu_bnepi.py tests/test_gpu_fullsize.py -k "bnepi or cinpad or 1080p" -m gpu -v --timeout 300 --timeout-method thread -p no:cacheprovider &&
          for i in 1 2; do run cp0_$i 200 env ROD_DISABLE=cinpad python tools/predict_bench.py --res 1080 --batch 8 --iters 30 && run cp1_$i 200 python tools/predict_bench.py --res 1080 --batch 8 --iters 30 && run cq0_$i 200 env ROD_DISABLE=cinpad python tools/predict_bench.py --res 720 --batch 32 --iters 20 && run cq1_$i 200 python tools/predict_bench.py --res 720 --batch 32 --iters 20; done;
          grep -H ms_per_batch $OUT/${TAG}_cp?_*.log $OUT/${TAG}_cq?_*.log ;;
     dwtable) run dwtable 300 python tools/dw_bench.py --ops fwd,fwdpro && grep -E "^fwd|TOTAL" $OUT/${TAG}_dwtable.log > $OUT/${TAG}_dw_fwd_table.txt ;;
-    slabab) run slabtest 400 env ROD_SLAB_POLICY=1 python -u -m pytest tests/test_gpu_defer.py tests/test_gpu_train.py -k "defer or refine" -m gpu -v --timeout 300 --timeout-method thread -p no:cacheprovider &&
-         for i in 1 2 3; do run sl0_$i 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run sl1_$i 300 env ROD_SLAB_POLICY=1 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0; done;
-         grep -H -o '"value": [0-9.]*' $OUT/${TAG}_sl?_*.log ;;
-    predprev) for i in 1 2; do run pp0_$i 200 env ROD_LIB=road-object-detection-for-bdd100k_amd/lib/librod_prev.so python tools/predict_bench.py --res 1080 --batch 8 --iters 30 && run pp1_$i 200 python tools/predict_bench.py --res 1080 --batch 8 --iters 30 && run pq0_$i 200 env ROD_LIB=road-object-detection-for-bdd100k_amd/lib/librod_prev.so python tools/predict_bench.py --res 720 --batch 32 --iters 20 && run pq1_$i 200 python tools/predict_bench.py --res 720 --batch 32 --iters 20; done;
-         grep -H ms_per_batch $OUT/${TAG}_pp?_*.log $OUT/${TAG}_pq?_*.log ;;
-    trprev) run trtest 400 python -u -m pytest tests/test_gpu_recompute.py tests/test_gpu_pwbwd.py -m gpu -q --timeout 300 --timeout-method thread -p no:cacheprovider &&
-         for i in 1 2 3; do run tp0_$i 300 env ROD_LIB=road-object-detection-for-bdd100k_amd/lib/librod_prev.so python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run tp1_$i 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0; done;
-         grep -H -o '"value": [0-9.]*' $OUT/${TAG}_tp?_*.log ;;
-    profab) run profa 300 env ROD_LIB=road-object-detection-for-bdd100k_amd/lib/librod_prev.so rocprofv3 --kernel-trace --stats -d $OUT/profa_$TAG -o run --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 &&
-         run profb 300 rocprofv3 --kernel-trace --stats -d $OUT/profb_$TAG -o run --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 &&
-         rm -f $OUT/profa_$TAG/run_kernel_trace.csv $OUT/profb_$TAG/run_kernel_trace.csv ;;
-    trprev2) run trtest2 400 python -u -m pytest tests/test_gpu_recompute.py tests/test_gpu_pwbwd.py -m gpu -q --timeout 300 --timeout-method thread -p no:cacheprovider &&
-         for i in 1 2; do run tq0_$i 300 env ROD_LIB=road-object-detection-for-bdd100k_amd/lib/librod_prev.so python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run tq1_$i 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0; done;
-         grep -H -o '"value": [0-9.]*' $OUT/${TAG}_tq?_*.log ;;
-    bnsmall) for v in 4 2 1; do run bnsmall_$v 200 env ROD_BN_SMALL_CVB=$v python tools/bn_bench.py --iters 20; done; grep -H -E "M= *(1920|480|120) |TOTAL" $OUT/${TAG}_bnsmall_*.log ;;
     tests) run tests 900 python -m pytest tests -m gpu -q -x --timeout=600 -p no:cacheprovider ;;
     testsall) run testsall 900 python -m pytest tests -m gpu -q --timeout=600 -p no:cacheprovider ;;
     clitest) run clitest 400 python -m pytest tests/test_gpu_fullsize.py -m gpu -q -k cli --timeout=300 -p no:cacheprovider ;;
-    merge) run merge 400 python -u -m pytest tests/test_gpu_merge.py tests/test_gpu_kernels.py tests/test_gpu_defer.py -k "merge or finalize or defer" -m gpu -v --timeout=300 --timeout-method thread -p no:cacheprovider &&
-        run mergedbg 300 env ROD_DEBUG_MERGE=1 python bench.py --steps 1 --warmup 1 --no-graph --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 ;;
+    merge) run merge 400 python -u -m pytest tests/test_gpu_merge.py tests/test_gpu_kernels.py tests/test_gpu_defer.py -k "merge or finalize or defer" -m gpu -v --timeout=300 --timeout-method thread -p no:cacheprovider ;;
     abmerge) for i in 1 2; do run abm2_$i 300 env ROD_MERGE_TWO_LAUNCH=1 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run abm1_$i 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0; done; grep -h '"value"' $OUT/${TAG}_abm*.log | cut -c1-60 ;;
     abproj) for i in 1 2; do run abp0_$i 300 env ROD_PW_PROJ=0 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run abp1_$i 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0; done; grep -h '"value"' $OUT/${TAG}_abp*.log | cut -c1-60 ;;
     cbproj) run cbproj0 300 env ROD_PW_PROJ=0 python tools/conv_bench.py --ops fwd_stats --shapes 1,3,16,17,18 &&
@@ -75,10 +46,7 @@ for step in "$@"; do
     cbdeep) run cbd0 300 env ROD_PW_PROJ=0 python tools/conv_bench.py --ops fwd_stats --shapes 16 &&
         run cbd2 300 python tools/conv_bench.py --ops fwd_stats --shapes 16 &&
         run cbexp 300 python tools/conv_bench.py --ops fwd_plain,fwd_stats --shapes 0,2,4 ;;
-    abprev) for i in 1 2; do run abq0_$i 300 env ROD_LIB=road-object-detection-for-bdd100k_amd/lib/librod_prev.so python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run abq1_$i 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0; done; grep -h '"value"' $OUT/${TAG}_abq*.log | cut -c1-60 ;;
-    abprev3) run abr0_1 300 env ROD_LIB=road-object-detection-for-bdd100k_amd/lib/librod_prev.so python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run abr1_1 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run abr1_2 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run abr0_2 300 env ROD_LIB=road-object-detection-for-bdd100k_amd/lib/librod_prev.so python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run abr0_3 300 env ROD_LIB=road-object-detection-for-bdd100k_amd/lib/librod_prev.so python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run abr1_3 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0; grep -h '"value"' $OUT/${TAG}_abr*.log | cut -c1-60 ;;
     abproj3) run abs0_1 300 env ROD_PW_PROJ=0 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run abs1_1 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run abs1_2 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run abs0_2 300 env ROD_PW_PROJ=0 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run abs0_3 300 env ROD_PW_PROJ=0 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run abs1_3 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0; grep -h '"value"' $OUT/${TAG}_abs*.log | cut -c1-60 ;;
-    absplit3) run abt0_1 300 env ROD_SPLIT_FUSE=0 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run abt1_1 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run abt1_2 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run abt0_2 300 env ROD_SPLIT_FUSE=0 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run abt0_3 300 env ROD_SPLIT_FUSE=0 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0 && run abt1_3 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-inference --no-fp32-leg --no-tfrecord-leg --no-dp-leg --kernel-steps 0; grep -h '"value"' $OUT/${TAG}_abt*.log | cut -c1-60 ;;
     splittest) run splittest 400 python -u -m pytest tests/test_gpu_splitk.py tests/test_gpu_bwd_data_bn.py tests/test_gpu_kernels.py -k "split or bwd_data or prologue" -m gpu -v --timeout=200 --timeout-method thread -p no:cacheprovider ;;
     streamtest) run streamtest 300 python -u -m pytest tests/test_gpu_pwproj.py tests/test_gpu_kernels.py -k "pw_stream or pw_proj or prologue" -m gpu -v --timeout=200 --timeout-method thread -p no:cacheprovider ;;
     projtest) run projtest 300 python -u -m pytest tests/test_gpu_pwproj.py -m gpu -v --timeout=200 --timeout-method thread -p no:cacheprovider ;;
@@ -88,26 +56,6 @@ for step in "$@"; do
     benchfp32) run benchfp32 600 python bench.py --full --dtype fp32 --steps 5 --warmup 2 --no-cpu-baseline --no-inference ;;
     hosttime) run hosttime 300 python tools/host_time.py --steps 10 ;;
     hostprof) run hostprof 300 python -m cProfile -s tottime tools/host_time.py --steps 5 ;;
-    bnu) run bnu4 300 python tools/bn_bench.py --out /tmp/${TAG}_bn4.pt && run bnu8 300 env ROD_BN_RED_U=8 python tools/bn_bench.py --check /tmp/${TAG}_bn4.pt ;;
-    bna) run bna4 300 python tools/bn_bench.py --out /tmp/${TAG}_bn4.pt && run bna8 300 env ROD_BN_APPLY_U=8 python tools/bn_bench.py --check /tmp/${TAG}_bn4.pt ;;
-    dwplan) run dwp0 300 python tools/dw_bench.py --out /tmp/${TAG}_dw.pt &&
-            run dwp1 300 env ROD_DW_WANT=2048 python tools/dw_bench.py --check /tmp/${TAG}_dw.pt &&
-            run dwp2 300 env ROD_DW_WANT=512 python tools/dw_bench.py --check /tmp/${TAG}_dw.pt &&
-            run dwp3 300 env ROD_DW_RBMIN=4 python tools/dw_bench.py --check /tmp/${TAG}_dw.pt &&
-            run dwp4 300 env ROD_DW_RBMIN=16 python tools/dw_bench.py --check /tmp/${TAG}_dw.pt ;;
-    dwplan2) run dwq0 300 python tools/dw_bench.py --out /tmp/${TAG}_dw.pt &&
-             run dwq1 300 env ROD_DW_RBMIN=16 python tools/dw_bench.py --check /tmp/${TAG}_dw.pt &&
-             run dwq2 300 env ROD_DW_RBMIN=24 python tools/dw_bench.py --check /tmp/${TAG}_dw.pt &&
-             run dwq3 300 env ROD_DW_RBMIN=32 python tools/dw_bench.py --check /tmp/${TAG}_dw.pt ;;
-    wgplan) run wg0 300 python tools/conv_bench.py --ops wgrad --out /tmp/${TAG}_wg.pt &&
-            run wg1 300 env ROD_WG_TARGET=4096 python tools/conv_bench.py --ops wgrad --check /tmp/${TAG}_wg.pt &&
-            run wg2 300 env ROD_WG_TARGET=1024 python tools/conv_bench.py --ops wgrad --check /tmp/${TAG}_wg.pt &&
-            run wg3 300 env ROD_WG_MINROWS=256 python tools/conv_bench.py --ops wgrad --check /tmp/${TAG}_wg.pt &&
-            run wg4 300 env ROD_WG_MINROWS=1024 python tools/conv_bench.py --ops wgrad --check /tmp/${TAG}_wg.pt ;;
-    bnwant) run bw0 300 python tools/bn_bench.py --out /tmp/${TAG}_bn.pt &&
-            run bw1 300 env ROD_BN_RED_WANT=2048 python tools/bn_bench.py --check /tmp/${TAG}_bn.pt &&
-            run bw2 300 env ROD_BN_RED_WANT=512 python tools/bn_bench.py --check /tmp/${TAG}_bn.pt &&
-            run bw3 300 env ROD_BN_RED_WANT=256 python tools/bn_bench.py --check /tmp/${TAG}_bn.pt ;;
     benchall) run benchall 600 python bench.py --full --steps 5 --warmup 2 --train_range ALL --no-cpu-baseline --no-inference ;;
     benchallfr) run benchallfr 600 python bench.py --full --steps 5 --warmup 2 --train_range ALL --no-fix-refine --no-cpu-baseline --no-inference ;;
     benchaug) run benchaug 600 python bench.py --full --steps 10 --warmup 3 --augment --no-cpu-baseline --no-inference --probe-table $OUT/${TAG}_probe_aug.json ;;
@@ -155,16 +103,12 @@ for step in "$@"; do
            python tools/pmc_kernel_summary.py $OUT/dwfpmc_$TAG/run_counter_collection.csv dw3x3_bwd_fused > $OUT/${TAG}_dwfpmc.txt &&
            gzip -f $OUT/dwfpmc_$TAG/run_counter_collection.csv && cat $OUT/${TAG}_dwfpmc.txt ;;
     dwfb) run dwfb 300 python tools/dwfused_bench.py ;;
-    pws) run pws0 300 env ROD_PW_STREAM=0 python tools/conv_bench.py --ops fwd_plain,fwd_stats --out /tmp/${TAG}_pws.pt &&
-         run pws1 300 python tools/conv_bench.py --ops fwd_plain,fwd_stats --check /tmp/${TAG}_pws.pt ;;
     bnpmc) run bnpmc 150 timeout -s KILL 140 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM SQ_INSTS_VALU SQ_WAVES SQ_BUSY_CYCLES -d $OUT/bnpmc_$TAG -o run --output-format csv -- python3 tools/bn_bench.py --iters 3 &&
            python tools/pmc_kernel_summary.py $OUT/bnpmc_$TAG/run_counter_collection.csv bn_ > $OUT/${TAG}_bnpmc.txt &&
            gzip -f $OUT/bnpmc_$TAG/run_counter_collection.csv && cat $OUT/${TAG}_bnpmc.txt ;;
     dwbench) run dwbench 300 python tools/dw_bench.py ;;
     bnbench) run bnbench 300 python tools/bn_bench.py ;;
     cbench) run cbench 300 python tools/conv_bench.py ;;
-    dwab) run dwa 300 env ROD_LIB=road-object-detection-for-bdd100k_amd/lib/librod_w0.so python tools/dw_bench.py --out /tmp/${TAG}_dw0.pt &&
-          run dwb 300 python tools/dw_bench.py --check /tmp/${TAG}_dw0.pt ;;
     dwbn) run dwbn 600 python -m pytest tests/test_gpu_dwbn.py tests/test_gpu_train.py tests/test_gpu_kernels.py -m gpu -q -x --timeout=500 -p no:cacheprovider ;;
     traintests) run traintests 800 python -m pytest tests/test_gpu_train.py tests/test_gpu_fullsize.py tests/test_gpu_vgg.py tests/test_gpu_msf.py tests/test_gpu_dp_equiv.py -m gpu -q -x --timeout=500 -p no:cacheprovider ;;
     irtests) run irtests 300 python -m pytest tests/test_gpu_irblock.py -m gpu -q -x --timeout=250 -p no:cacheprovider ;;
