@@ -10,6 +10,7 @@
 // is a contiguous, 16-byte-per-lane coalesced segment.
 #include "rod_common.h"
 #include "dw_common.h"
+#include "dwfused_common.h"
 
 namespace rod {
 
@@ -1589,11 +1590,8 @@ int rod_dw3x3_bwd_filter_bn(const void* x, const float* pro_mean, const float* p
 //     clamped, always-valid column, computes dx / filter / BN_e sums, and only the dx store is
 //     predicated on `comp`; halo sums are dropped by the column reduction as before.  Row
 //     conditions are block-uniform (scalar branches);
-//   * channel pairs run as packed f32 ops (v_pk_fma / v_pk_mul / v_pk_add, per element the same
-//     operation in the same order);
-//   * the activation gradients are specialised (ReLU6: one compare pair + select), and the
-//     BN_e gradient mask comes from the prologue's own z (the x element of the same row);
-//   * yhat_e = fma(ye, rstd, -mean * rstd) (the stride-2 kernel's form).
+//   * the per-element arithmetic (packed channel pairs, specialised gates, the BN_e gate from the
+//     prologue's own z) is dwfused_common.h's, shared with the stride-2 kernels: see there.
 
 // Project-gradient recompute (PW, ABI 20: rod_dw3x3_bwd_fused_pw).  In an inverted-residual block
 // dz — the gradient at act_d(BN_d(yd)), i.e. at the project conv's input — is dy_p . W_p with dy_p
@@ -1610,10 +1608,10 @@ struct DwPw {
   const bf16_t* wt1;   // [C][cout]: W_p^T, the project conv's mode-1 GEMM layout
   int cout;
 };
-constexpr int DWPW_LD = 52;
-#ifndef DW_QG_PW
-#define DW_QG_PW 6
-#endif   // LDS row stride (bf16) of the recomputed dz tile: <= 48 channels + pad
+constexpr int DWPW_LD = 52;   // LDS row stride (bf16) of the recomputed dz tile: <= 48 channels + pad
+// PW's row loop is at the 128-VGPR bound and spills with the all-at-once epilogue: it stages this
+// many quantities a round (dwf_epilogue)
+constexpr int DW_QG_PW = 6;
 
 // V = 2 (bf16): the same tile with twice the threads (512 per block), each holding 2 channels —
 // half the per-thread weights, accumulators and BatchNorm constants, twice the waves in flight;
@@ -1633,66 +1631,30 @@ __global__ void __launch_bounds__(1024 / V, PW ? 4 : 1) dw3x3_bwd_fused2_kernel(
   // slots, one per step of the 3-step body, so every LDS address is the thread's base plus a
   // compile-time offset
   constexpr int XS = 3 * 2 * TB * VP * (int)sizeof(dw_f2);
-  // the epilogue's staged column sums: all at once (dw_colsum_emit), or — PW, whose main loop
-  // is at the 128-VGPR bound and spills with the one-barrier epilogue — DW_QG_PW at a time
-  constexpr int SS = (PW ? DW_QG_PW : (RED ? 11 : 9)) * TB * V * 4;
+  // the epilogue's staged column sums: all at once, or (PW) DW_QG_PW at a time
+  constexpr int QG = PW ? DW_QG_PW : (RED ? 11 : 9);
+  constexpr int SS = QG * TB * V * 4;
   __shared__ __attribute__((aligned(16))) char smem[XS > SS ? XS : SS];
   dw_f2* xs = (dw_f2*)smem;
   dw_f2* dsl = xs + 3 * TB * VP;
-  const int tid = threadIdx.x;
-  const int CVb = tl.CVb * (4 / V), P = tl.P;
-  const int p = tid / CVb, cvb = tid - (tid / CVb) * CVb;
-  int bx, strip, n;
-  xcd_block(bx, strip, n);
-  const int cg = bx % tl.cgroups, ct = bx / tl.cgroups;
-  const int c = (cg * CVb + cvb) * V;
+  DwfPos<V> at;
+  at.init(tl);
+  const int tid = at.tid, CVb = at.CVb, P = at.P, p = at.p, cvb = at.cvb;
+  const int strip = at.strip, n = at.n, cg = at.cg, ct = at.ct, c = at.c, li = at.li, ri = at.ri;
   const int col = ct * tl.TWo + p - 1;
   const bool comp = p >= 1 && p <= P - 2 && col < W;
   const bool cok = p < P && col >= 0 && col < W;
   const int colc = col < 0 ? 0 : (col >= W ? W - 1 : col);         // always a valid address
-  const int li = tid >= CVb ? tid - CVb : tid, ri = tid + CVb < TB ? tid + CVb : tid;
   const int ho0 = strip * tl.RB;
   const int ho1 = ho0 + tl.RB < H ? ho0 + tl.RB : H;
   const int xlo = ho0 - 1 > 0 ? ho0 - 1 : 0, xhi = ho1 < H - 1 ? ho1 : H - 1;
 
   dw_f2 wr[9][VP];
-#pragma unroll
-  for (int k = 0; k < 9; ++k)
-#pragma unroll
-    for (int h = 0; h < VP; ++h) wr[k][h] = dw_f2{w[k * C + c + 2 * h], w[k * C + c + 2 * h + 1]};
-  dw_f2 psc[VP], psh[VP], ers[VP], enb[VP];
-  int pact = 0;
-  if constexpr (PACT >= 0) {
-    pact = pro.act;
-#pragma unroll
-    for (int h = 0; h < VP; ++h) {
-      float a0, b0, a1, b1;
-      bn_pro_affine(pro, c + 2 * h, a0, b0);
-      bn_pro_affine(pro, c + 2 * h + 1, a1, b1);
-      psc[h] = dw_f2{a0, a1};
-      psh[h] = dw_f2{b0, b1};
-      if constexpr (RED) {
-        ers[h] = dw_f2{pro.rstd[c + 2 * h], pro.rstd[c + 2 * h + 1]};
-        enb[h] = dw_f2{-pro.mean[c + 2 * h] * ers[h].x, -pro.mean[c + 2 * h + 1] * ers[h].y};
-      }
-    }
-  }
-  dw_f2 dsc[VP], dsh[VP], da[VP], dmg[VP], dmx[VP], dmm[VP];
-#pragma unroll
-  for (int h = 0; h < VP; ++h) {
-    const int c0 = c + 2 * h;
-    float s0, t0, s1, t1, k10, k00, k11, k01, m0, m1;
-    bn_affine(bd.mean, bd.rstd, bd.gamma, bd.beta, c0, s0, t0);
-    bn_affine(bd.mean, bd.rstd, bd.gamma, bd.beta, c0 + 1, s1, t1);
-    dsc[h] = dw_f2{s0, s1};
-    dsh[h] = dw_f2{t0, t1};
-    da[h] = dw_f2{bd.coef[c0], bd.coef[c0 + 1]};
-    bn_bwd_k<T>(da[h].x, bd.mean[c0], bd.rstd[c0], bd.coef[C + c0], bd.coef[2 * C + c0], k10, k00, m0);
-    bn_bwd_k<T>(da[h].y, bd.mean[c0 + 1], bd.rstd[c0 + 1], bd.coef[C + c0 + 1], bd.coef[2 * C + c0 + 1], k11, k01, m1);
-    dmg[h] = dw_f2{k10, k11};   // the apply's k1 / k0 / centring shift (bn_bwd_k)
-    dmx[h] = dw_f2{k00, k01};
-    dmm[h] = dw_f2{m0, m1};
-  }
+  dwf_taps(w, C, c, wr);
+  DwfBnE<VP, PACT, RED> bne;
+  bne.init(pro, c);
+  DwfBnD<T, VP, BACT> bnd;
+  bnd.init(bd, C, c);
   dw_f2 sg[VP], sgx[VP];
 #pragma unroll
   for (int h = 0; h < VP; ++h) sg[h] = sgx[h] = dw_f2{0.f, 0.f};
@@ -1794,18 +1756,7 @@ __global__ void __launch_bounds__(1024 / V, PW ? 4 : 1) dw3x3_bwd_fused2_kernel(
       unpackv(rx[k], yr);
 #pragma unroll
       for (int h = 0; h < VP; ++h) {
-        dw_f2 a = yr[h];
-        if constexpr (PACT >= 0) {
-          const dw_f2 z = f2fma(a, psc[h], psh[h]);
-          dw_f2 t;
-          if constexpr (PACT == ROD_ACT_RELU6) {
-            t = dw_f2{act_t<ROD_ACT_RELU6>(z.x), act_t<ROD_ACT_RELU6>(z.y)};
-          } else {
-            t = dw_f2{act_fwd(z.x, pact), act_fwd(z.y, pact)};
-          }
-          a = round2(t, T{});
-          if constexpr (RED) em[h] = z;   // BN_e's pre-activation: the gradient gate of this element
-        }
+        const dw_f2 a = bne.x_of(h, yr[h], em[h], T{});
         xv[h] = xok ? a : dw_f2{0.f, 0.f};
       }
       // dy row rho + 1: BN_d backward apply (rod_bn_bwd_apply's arithmetic), rounded to T
@@ -1820,14 +1771,7 @@ __global__ void __launch_bounds__(1024 / V, PW ? 4 : 1) dw3x3_bwd_fused2_kernel(
           unpackv(rz[k], zv);
         }
 #pragma unroll
-        for (int h = 0; h < VP; ++h) {
-          const dw_f2 z = f2fma(yv[h], dsc[h], dsh[h]);
-          const dw_f2 g = gate2<BACT>(z, zv[h], bd.act);
-          // bn_bwd_apply1<T>, pairwise
-          const dw_f2 yc = sizeof(T) == 4 ? yv[h] - dmm[h] : yv[h];
-          const dw_f2 o = f2fma(da[h], g, f2fma(dmg[h], yc, dmx[h]));
-          dv[h] = dok ? round2(o, T{}) : dw_f2{0.f, 0.f};
-        }
+        for (int h = 0; h < VP; ++h) dv[h] = dok ? round2(bnd.dy_of(h, yv[h], zv[h]), T{}) : dw_f2{0.f, 0.f};
       }
       // keep the ring slot's reload after its last read: the scheduler hoisting it would make the
       // slot's old and new values overlap, and the copy that resolves that at the loop back-edge
@@ -1883,25 +1827,11 @@ __global__ void __launch_bounds__(1024 / V, PW ? 4 : 1) dw3x3_bwd_fused2_kernel(
       const bool rowout = rho >= ho0 && rho < ho1;
       PK o;
 #pragma unroll
-      for (int h = 0; h < VP; ++h) {
-        if constexpr (sizeof(T) == 2) {   // one v_cvt_pk_bf16_f32 per pair
-          const dw_b2 b = __builtin_convertvector(acc[k3][h], dw_b2);
-          o.v[2 * h] = b.x;
-          o.v[2 * h + 1] = b.y;
-        } else {
-          o.set(2 * h, acc[k3][h].x);
-          o.set(2 * h + 1, acc[k3][h].y);
-        }
-      }
+      for (int h = 0; h < VP; ++h) dwf_dx_pair(o, h, acc[k3][h]);
       if (rowout) {   // BN_e sums from the rounded dx, before the store (its last use)
         if constexpr (RED) {
 #pragma unroll
-          for (int h = 0; h < VP; ++h) {
-            const dw_f2 ov = dw_f2{o.get(2 * h), o.get(2 * h + 1)};
-            const dw_f2 g = gate2<PACT>(em[h], ov, pact);
-            sg[h] += g;
-            sgx[h] = f2fma(g, f2fma(yr[h], ers[h], enb[h]), sgx[h]);
-          }
+          for (int h = 0; h < VP; ++h) bne.sum(h, sg[h], sgx[h], em[h], dwf_dx_stored(o, h), yr[h]);
         }
       }
       o.bstore(rowout ? rdx : rnull, vox, (unsigned)(rho < 0 ? 0 : rho) * rstrb);
@@ -1910,14 +1840,13 @@ __global__ void __launch_bounds__(1024 / V, PW ? 4 : 1) dw3x3_bwd_fused2_kernel(
     }
   }
 
+  // the grouped epilogue (QG quantities a round) is this kernel's alone and stays inline: as a call
+  // the PW form, at the 128-VGPR bound, spilled one register (profiles/dwfused_share_resources.md)
   __syncthreads();
   float* red = (float*)smem;
   const int Cc = CVb * V;
   const long part = ((long)n * tl.strips + strip) * tl.coltiles + ct;
   constexpr int NQ = RED ? 11 : 9;
-  // quantities per staging round: all at once, or (PW, whose row loop runs at the 128-VGPR
-  // bound and spills with an all-at-once epilogue) QG_PW at a time
-  constexpr int QG = PW ? DW_QG_PW : NQ;
   auto stage = [&](const dw_f2 (&a)[VP], int slot) {
 #pragma unroll
     for (int h = 0; h < VP; ++h) {
@@ -1964,23 +1893,9 @@ __global__ void __launch_bounds__(256, 2) dw3x3_bwd_fused_s2_kernel(const float*
   PK* dsl = (PK*)smem;         // [2][256]
   PK* x0s = dsl + 2 * 256;     // [2][256]
   PK* x1s = x0s + 2 * 256;     // [2][256]
-  const int tid = threadIdx.x;
-  const int CVb = tl.CVb, P = tl.P;
-  const int p = tid / CVb, cvb = tid - (tid / CVb) * CVb;
-  int bx, strip, n;
-  xcd_block(bx, strip, n);
-  const int cg = bx % tl.cgroups, ct = bx / tl.cgroups;
-  const int c = (cg * CVb + cvb) * V;
-  const int b = ct * tl.TWo + p - 1;
-  const int ci0 = 2 * b - pl;
-  // the tiled map is (A, B): every a / b with a dx row / column (dy rows >= Ho read as zero)
-  const int A = ((H - 1 + pt) >> 1) + 1, B = ((W - 1 + pl) >> 1) + 1;
-  const bool comp = p >= 1 && p <= P - 2 && b < B;
-  const bool cokd = p < P && b >= 0 && b < Wo;
-  const bool cok0 = p < P && ci0 >= 0 && ci0 < W;
-  const bool cok1 = p < P && ci0 + 1 >= 0 && ci0 + 1 < W;
-  const int a0 = strip * tl.RB;
-  const int a1 = a0 + tl.RB < A ? a0 + tl.RB : A;
+  DwfPos<V> at;
+  at.init(tl);
+  const int tid = at.tid, CVb = at.CVb, P = at.P, cg = at.cg, c = at.c;
 
   float wr[9][V];
 #pragma unroll
@@ -1989,66 +1904,21 @@ __global__ void __launch_bounds__(256, 2) dw3x3_bwd_fused_s2_kernel(const float*
     for (int v = 0; v < V; ++v) wr[k][v] = w[k * C + c + v];
   DwIn<T, V, PACT> in;
   in.init(pro, c);
-  float dsc[V], dsh[V], da[V], dmg[V], dmx[V], dmm[V];   // dmg / dmx / dmm: the apply's k1 / k0 / m
-#pragma unroll
-  for (int v = 0; v < V; ++v) {
-    bn_affine(bd.mean, bd.rstd, bd.gamma, bd.beta, c + v, dsc[v], dsh[v]);
-    da[v] = bd.coef[c + v];
-    bn_bwd_k<T>(da[v], bd.mean[c + v], bd.rstd[c + v], bd.coef[C + c + v], bd.coef[2 * C + c + v], dmg[v], dmx[v],
-                dmm[v]);
-  }
+  // both BatchNorms' constants from the shared set-up; the scalar body reads them per channel
+  DwfBnD<T, V / 2, DW_ACT_RT> bnd;
+  bnd.init(bd, C, c);
+  DwfBnE<V / 2, PACT, RED> bne;
+  bne.init(pro, c);
   constexpr int RV = RED ? V : 1;
-  float enb[RV], ers[RV], sg[RV], sgx[RV];  // xhat_e = fma(y_e, rstd, -mean * rstd)
-  if constexpr (RED) {
+  float sg[RV], sgx[RV];
 #pragma unroll
-    for (int v = 0; v < V; ++v) {
-      ers[v] = pro.rstd[c + v];
-      enb[v] = -pro.mean[c + v] * ers[v];
-      sg[v] = sgx[v] = 0.f;
-    }
-  }
-  // buffer resources over this image; every load is issued (rows / columns clamped into the
-  // map, uses masked by okd / okx) and every dx store too (vo = ROD_OOB where nothing is to be
-  // written), so the wait counts of the prefetch ring stay exact (see rod_common.h)
-  const unsigned es = sizeof(T);
-  const rsrc_t rye = rod_rsrc(ye + (long)n * H * W * C, (unsigned)((long)H * W * C * es));
-  const rsrc_t rdx = rod_rsrc(dx + (long)n * H * W * C, (unsigned)((long)H * W * C * es));
-  const rsrc_t rnull = rod_rsrc(dx + (long)n * H * W * C, 0u);
-  const rsrc_t rdz = rod_rsrc(dz + (long)n * Ho * Wo * C, (unsigned)((long)Ho * Wo * C * es));
-  const rsrc_t ryd = rod_rsrc(yd + (long)n * Ho * Wo * C, (unsigned)((long)Ho * Wo * C * es));
-  const int bc = b < 0 ? 0 : (b >= Wo ? Wo - 1 : b);
-  const int x0c = ci0 < 0 ? 0 : (ci0 >= W ? W - 1 : ci0), x1c = ci0 + 1 < 0 ? 0 : (ci0 + 1 >= W ? W - 1 : ci0 + 1);
-  const unsigned vod = (unsigned)(((long)bc * C + c) * es);
-  const unsigned vox0 = (unsigned)(((long)x0c * C + c) * es), vox1 = (unsigned)(((long)x1c * C + c) * es);
-  const unsigned vst0 = comp && cok0 ? vox0 : ROD_OOB, vst1 = comp && cok1 ? vox1 : ROD_OOB;
-  const unsigned rsx = (unsigned)(W * C * es), rsd = (unsigned)(Wo * C * es);
-
-  // ring slot: dy (dz, yd) of row a, x (ye) at rows 2a-pt, 2a+1-pt x columns ci0, ci0+1
-  PK rz[D], ry[D], rx[D][4];
-  bool okd[D], okx[D][4];
-  const int dlo = a0 - 1 > 0 ? a0 - 1 : 0;
-  const int dhi = a1 - 1 < Ho - 1 ? a1 - 1 : Ho - 1;
-  auto issue = [&](int k, int q) {
-    const int a = a0 - 1 + q;
-    okd[k] = cokd && a >= dlo && a <= dhi;
-    const int ac = a < dlo ? dlo : (a > dhi ? dhi : a);
-    rz[k].bload(rdz, vod, (unsigned)ac * rsd);
-    ry[k].bload(ryd, vod, (unsigned)ac * rsd);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int h = 2 * a - pt + (i >> 1);
-      const bool rowok = a >= a0 && (i < 2 ? a <= a1 : a < a1) && h >= 0 && h < H;
-      okx[k][i] = rowok && ((i & 1) ? cok1 : cok0);
-      const int hc = h < 0 ? 0 : (h >= H ? H - 1 : h);
-      rx[k][i].bload(rye, (i & 1) ? vox1 : vox0, (unsigned)hc * rsx);
-    }
-  };
-  const int nst = a1 - a0 + 2;
-#pragma unroll
-  for (int k = 0; k < D; ++k) {   // slot order (the loop header's wait is then the same on entry)
-    issue(k, k);
-    __builtin_amdgcn_sched_barrier(0);
-  }
+  for (int v = 0; v < RV; ++v) sg[v] = sgx[v] = 0.f;
+  DwfS2<T, V, D> geo;   // thread geometry, buffer resources and the prefetch ring (dwfused_common.h)
+  geo.init(at, ye, dz, yd, dx, tl, H, W, C, pt, pl, Ho, Wo);
+  const int a0 = geo.a0, a1 = geo.a1;
+  const bool comp = geo.comp;
+  const int nst = geo.steps();
+  geo.prime();
   float fa[9][V], pv[V], pL[V];
 #pragma unroll
   for (int v = 0; v < V; ++v) {
@@ -2065,20 +1935,21 @@ __global__ void __launch_bounds__(256, 2) dw3x3_bwd_fused_s2_kernel(const float*
       float dv[V];
 #pragma unroll
       for (int v = 0; v < V; ++v) {
-        const float yv = ry[k].get(v);
-        const float z = fmaf(yv, dsc[v], dsh[v]);
-        const float g = rz[k].get(v) * act_grad(z, bd.act);
-        const float o = bn_bwd_apply1<T>(da[v], g, dmg[v], dmx[v], dmm[v], yv);
-        dv[v] = okd[k] ? to_f32(from_f32<T>(o)) : 0.f;
+        const float yv = geo.ry[k].get(v);
+        const float z = fmaf(yv, dwf_lane(bnd.dsc, v), dwf_lane(bnd.dsh, v));
+        const float g = geo.rz[k].get(v) * act_grad(z, bd.act);
+        const float o = bn_bwd_apply1<T>(dwf_lane(bnd.da, v), g, dwf_lane(bnd.k1, v), dwf_lane(bnd.k0, v),
+                                         dwf_lane(bnd.m, v), yv);
+        dv[v] = geo.okd[k] ? to_f32(from_f32<T>(o)) : 0.f;
       }
       float xv[4][V], yr[4][V];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        in.cvt(rx[k][i], okx[k][i], xv[i]);
+        in.cvt(geo.rx[k][i], geo.okx[k][i], xv[i]);
 #pragma unroll
         for (int v = 0; v < V; ++v) {
-          if constexpr (PACT < 0) xv[i][v] = okx[k][i] ? xv[i][v] : 0.f;
-          yr[i][v] = rx[k][i].get(v);
+          if constexpr (PACT < 0) xv[i][v] = geo.okx[k][i] ? xv[i][v] : 0.f;
+          yr[i][v] = geo.rx[k][i].get(v);
         }
       }
       PK pd, p0, p1;
@@ -2089,7 +1960,7 @@ __global__ void __launch_bounds__(256, 2) dw3x3_bwd_fused_s2_kernel(const float*
         p1.set(v, xv[2][v]);
       }
       __builtin_amdgcn_sched_barrier(0);   // the slots' reloads stay after their last reads
-      issue(k, q + D);
+      geo.issue(k, q + D);
       dsl[buf * 256 + tid] = pd;
       x0s[buf * 256 + tid] = p0;
       x1s[buf * 256 + tid] = p1;
@@ -2097,7 +1968,7 @@ __global__ void __launch_bounds__(256, 2) dw3x3_bwd_fused_s2_kernel(const float*
       {
         // every lane computes (halo lanes' results are dropped: stores out of range, column sums
         // masked by comp), so no memory operation sits under a branch
-        const int li = tid >= CVb ? tid - CVb : tid, ri = tid + CVb < 256 ? tid + CVb : tid;
+        const int li = at.li, ri = at.ri;
         const PK dlp = dsl[buf * 256 + li];
         const PK r0 = x0s[buf * 256 + ri], r1 = x1s[buf * 256 + ri];
         float dL[V];
@@ -2123,17 +1994,17 @@ __global__ void __launch_bounds__(256, 2) dw3x3_bwd_fused_s2_kernel(const float*
           for (int v = 0; v < V; ++v) pk.set(v, o[i][v]);
           if constexpr (RED) {   // BN_e sums from the rounded dx, before the store (its last use)
             if (hok) {
-              const bool cc = (i & 1) ? cok1 : cok0;
+              const bool cc = (i & 1) ? geo.cok1 : geo.cok0;
 #pragma unroll
               for (int v = 0; v < V; ++v) {
                 const float z = fmaf(yr[i][v], in.sc[v], in.sh[v]);
                 const float g = cc ? pk.get(v) * act_grad(z, pro.act) : 0.f;
                 sg[v] += g;
-                sgx[v] = fmaf(g, fmaf(yr[i][v], ers[v], enb[v]), sgx[v]);
+                sgx[v] = fmaf(g, fmaf(yr[i][v], dwf_lane(bne.ers, v), dwf_lane(bne.enb, v)), sgx[v]);
               }
             }
           }
-          pk.bstore(hok ? rdx : rnull, (i & 1) ? vst1 : vst0, (unsigned)(hok ? h : 0) * rsx);
+          geo.store(pk, i, hok, h);
         }
         // filter: dy[a] with x rows 2a-pt (tap row 0) and 2a+1-pt (1), dy[a-1] with 2a-pt (2)
 #pragma unroll
@@ -2159,7 +2030,7 @@ __global__ void __launch_bounds__(256, 2) dw3x3_bwd_fused_s2_kernel(const float*
   __syncthreads();
   float* red = (float*)smem;
   const int Cc = CVb * V;
-  const long part = ((long)n * tl.strips + strip) * tl.coltiles + ct;
+  const long part = at.part(tl);
   auto colsum = [&](const float (&acc)[V], float* dst) {
 #pragma unroll
     for (int v = 0; v < V; ++v) red[tid * V + v] = comp ? acc[v] : 0.f;
@@ -2202,105 +2073,25 @@ __global__ void __launch_bounds__(1024 / V, V == 4 ? 2 : 1) dw3x3_bwd_fused_s2p_
   constexpr int SS = (RED ? 11 : 9) * TB * V * 4;   // the epilogue's staged column sums
   __shared__ __attribute__((aligned(16))) char smem[XS > SS ? XS : SS];
   dw_f2* sl = (dw_f2*)smem;
-  const int tid = threadIdx.x;
-  const int CVb = tl.CVb * (4 / V), P = tl.P;
-  const int p = tid / CVb, cvb = tid - (tid / CVb) * CVb;
-  int bx, strip, n;
-  xcd_block(bx, strip, n);
-  const int cg = bx % tl.cgroups, ct = bx / tl.cgroups;
-  const int c = (cg * CVb + cvb) * V;
-  const int b = ct * tl.TWo + p - 1;
-  const int ci0 = 2 * b - pl;
-  const int A = ((H - 1 + pt) >> 1) + 1, B = ((W - 1 + pl) >> 1) + 1;
-  const bool comp = p >= 1 && p <= P - 2 && b < B;
-  const bool cokd = p < P && b >= 0 && b < Wo;
-  const bool cok0 = p < P && ci0 >= 0 && ci0 < W;
-  const bool cok1 = p < P && ci0 + 1 >= 0 && ci0 + 1 < W;
-  const int a0 = strip * tl.RB;
-  const int a1 = a0 + tl.RB < A ? a0 + tl.RB : A;
-  const int li = tid >= CVb ? tid - CVb : tid, ri = tid + CVb < TB ? tid + CVb : tid;
+  DwfPos<V> at;
+  at.init(tl);
+  const int tid = at.tid, c = at.c, li = at.li, ri = at.ri;
 
   dw_f2 wr[9][VP];
-#pragma unroll
-  for (int k = 0; k < 9; ++k)
-#pragma unroll
-    for (int h = 0; h < VP; ++h) wr[k][h] = dw_f2{w[k * C + c + 2 * h], w[k * C + c + 2 * h + 1]};
-  dw_f2 psc[VP], psh[VP], ers[VP], enb[VP];
-  int pact = 0;
-  if constexpr (PACT >= 0) {
-    pact = pro.act;
-#pragma unroll
-    for (int h = 0; h < VP; ++h) {
-      float a0_, b0_, a1_, b1_;
-      bn_pro_affine(pro, c + 2 * h, a0_, b0_);
-      bn_pro_affine(pro, c + 2 * h + 1, a1_, b1_);
-      psc[h] = dw_f2{a0_, a1_};
-      psh[h] = dw_f2{b0_, b1_};
-      if constexpr (RED) {
-        ers[h] = dw_f2{pro.rstd[c + 2 * h], pro.rstd[c + 2 * h + 1]};
-        enb[h] = dw_f2{-pro.mean[c + 2 * h] * ers[h].x, -pro.mean[c + 2 * h + 1] * ers[h].y};
-      }
-    }
-  }
-  dw_f2 dsc[VP], dsh[VP], da[VP], dk1[VP], dk0[VP];
-#pragma unroll
-  for (int h = 0; h < VP; ++h) {
-    const int c0 = c + 2 * h;
-    float s0, t0, s1, t1, k10, k00, k11, k01;
-    bn_affine(bd.mean, bd.rstd, bd.gamma, bd.beta, c0, s0, t0);
-    bn_affine(bd.mean, bd.rstd, bd.gamma, bd.beta, c0 + 1, s1, t1);
-    dsc[h] = dw_f2{s0, s1};
-    dsh[h] = dw_f2{t0, t1};
-    da[h] = dw_f2{bd.coef[c0], bd.coef[c0 + 1]};
-    float m0, m1;   // bf16 storage: the folded form (m unused)
-    bn_bwd_k<bf16_t>(da[h].x, bd.mean[c0], bd.rstd[c0], bd.coef[C + c0], bd.coef[2 * C + c0], k10, k00, m0);
-    bn_bwd_k<bf16_t>(da[h].y, bd.mean[c0 + 1], bd.rstd[c0 + 1], bd.coef[C + c0 + 1], bd.coef[2 * C + c0 + 1], k11, k01,
-                     m1);
-    dk1[h] = dw_f2{k10, k11};
-    dk0[h] = dw_f2{k00, k01};
-  }
+  dwf_taps(w, C, c, wr);
+  DwfBnE<VP, PACT, RED> bne;
+  bne.init(pro, c);
+  DwfBnD<T, VP, BACT> bnd;
+  bnd.init(bd, C, c);
   dw_f2 sg[VP], sgx[VP];
 #pragma unroll
   for (int h = 0; h < VP; ++h) sg[h] = sgx[h] = dw_f2{0.f, 0.f};
 
-  const unsigned es = sizeof(T);
-  const rsrc_t rye = rod_rsrc(ye + (long)n * H * W * C, (unsigned)((long)H * W * C * es));
-  const rsrc_t rdx = rod_rsrc(dx + (long)n * H * W * C, (unsigned)((long)H * W * C * es));
-  const rsrc_t rnull = rod_rsrc(dx + (long)n * H * W * C, 0u);
-  const rsrc_t rdz = rod_rsrc(dz + (long)n * Ho * Wo * C, (unsigned)((long)Ho * Wo * C * es));
-  const rsrc_t ryd = rod_rsrc(yd + (long)n * Ho * Wo * C, (unsigned)((long)Ho * Wo * C * es));
-  const int bc = b < 0 ? 0 : (b >= Wo ? Wo - 1 : b);
-  const int x0c = ci0 < 0 ? 0 : (ci0 >= W ? W - 1 : ci0), x1c = ci0 + 1 < 0 ? 0 : (ci0 + 1 >= W ? W - 1 : ci0 + 1);
-  const unsigned vod = (unsigned)(((long)bc * C + c) * es);
-  const unsigned vox0 = (unsigned)(((long)x0c * C + c) * es), vox1 = (unsigned)(((long)x1c * C + c) * es);
-  const unsigned vst0 = comp && cok0 ? vox0 : ROD_OOB, vst1 = comp && cok1 ? vox1 : ROD_OOB;
-  const unsigned rsx = (unsigned)(W * C * es), rsd = (unsigned)(Wo * C * es);
-
-  PK rz[D], ry[D], rx[D][4];
-  bool okd[D], okx[D][4];
-  const int dlo = a0 - 1 > 0 ? a0 - 1 : 0;
-  const int dhi = a1 - 1 < Ho - 1 ? a1 - 1 : Ho - 1;
-  auto issue = [&](int k, int q) {
-    const int a = a0 - 1 + q;
-    okd[k] = cokd && a >= dlo && a <= dhi;
-    const int ac = a < dlo ? dlo : (a > dhi ? dhi : a);
-    rz[k].bload(rdz, vod, (unsigned)ac * rsd);
-    ry[k].bload(ryd, vod, (unsigned)ac * rsd);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int hh = 2 * a - pt + (i >> 1);
-      const bool rowok = a >= a0 && (i < 2 ? a <= a1 : a < a1) && hh >= 0 && hh < H;
-      okx[k][i] = rowok && ((i & 1) ? cok1 : cok0);
-      const int hc = hh < 0 ? 0 : (hh >= H ? H - 1 : hh);
-      rx[k][i].bload(rye, (i & 1) ? vox1 : vox0, (unsigned)hc * rsx);
-    }
-  };
-  const int nst = a1 - a0 + 2;
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    issue(k, k);
-    __builtin_amdgcn_sched_barrier(0);
-  }
+  DwfS2<T, V, D> geo;   // thread geometry, buffer resources and the prefetch ring (dwfused_common.h)
+  geo.init(at, ye, dz, yd, dx, tl, H, W, C, pt, pl, Ho, Wo);
+  const int a0 = geo.a0, a1 = geo.a1;
+  const int nst = geo.steps();
+  geo.prime();
   dw_f2 fa[9][VP], pv[VP], pL[VP];
 #pragma unroll
   for (int h = 0; h < VP; ++h) {
@@ -2318,37 +2109,24 @@ __global__ void __launch_bounds__(1024 / V, V == 4 ? 2 : 1) dw3x3_bwd_fused_s2p_
       dw_f2 dv[VP];
       {
         dw_f2 yv[VP], zv[VP];
-        unpackv(ry[k], yv);
-        unpackv(rz[k], zv);
+        unpackv(geo.ry[k], yv);
+        unpackv(geo.rz[k], zv);
 #pragma unroll
-        for (int h = 0; h < VP; ++h) {
-          const dw_f2 z = f2fma(yv[h], dsc[h], dsh[h]);
-          const dw_f2 g = gate2<BACT>(z, zv[h], bd.act);
-          const dw_f2 o = f2fma(da[h], g, f2fma(dk1[h], yv[h], dk0[h]));
-          dv[h] = okd[k] ? round2(o, T{}) : zero2;
-        }
+        for (int h = 0; h < VP; ++h) dv[h] = geo.okd[k] ? round2(bnd.dy_of(h, yv[h], zv[h]), T{}) : zero2;
       }
       // x at the 4 positions (prologue, rounded) and, with RED, BN_e's pre-activation (the gate)
       dw_f2 xv[4][VP], yr[4][VP], ez[4][VP];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        unpackv(rx[k][i], yr[i]);
+        unpackv(geo.rx[k][i], yr[i]);
 #pragma unroll
         for (int h = 0; h < VP; ++h) {
-          dw_f2 av = yr[i][h];
-          if constexpr (PACT >= 0) {
-            const dw_f2 z = f2fma(av, psc[h], psh[h]);
-            dw_f2 t;
-            if constexpr (PACT == ROD_ACT_RELU6) t = dw_f2{act_t<ROD_ACT_RELU6>(z.x), act_t<ROD_ACT_RELU6>(z.y)};
-            else t = dw_f2{act_fwd(z.x, pact), act_fwd(z.y, pact)};
-            av = round2(t, T{});
-            if constexpr (RED) ez[i][h] = z;
-          }
-          xv[i][h] = okx[k][i] ? av : zero2;
+          const dw_f2 av = bne.x_of(h, yr[i][h], ez[i][h], T{});
+          xv[i][h] = geo.okx[k][i] ? av : zero2;
         }
       }
       __builtin_amdgcn_sched_barrier(0);   // the slots' reloads stay after their last reads
-      issue(k, q + D);
+      geo.issue(k, q + D);
       dw_f2* S = sl + k * 3 * TB * VP;
 #pragma unroll
       for (int h = 0; h < VP; ++h) {
@@ -2380,27 +2158,16 @@ __global__ void __launch_bounds__(1024 / V, V == 4 ? 2 : 1) dw3x3_bwd_fused_s2p_
           else o[h] = c1 * wr[4][h];
         }
         PK pk;
-        dw_f2 orr[VP];
 #pragma unroll
-        for (int h = 0; h < VP; ++h) {
-          const dw_b2 bb = __builtin_convertvector(o[h], dw_b2);
-          pk.v[2 * h] = bb.x;
-          pk.v[2 * h + 1] = bb.y;
-          const unsigned u = __builtin_bit_cast(unsigned, bb);
-          orr[h] = dw_f2{__builtin_bit_cast(float, u << 16), __builtin_bit_cast(float, u & 0xffff0000u)};
-        }
+        for (int h = 0; h < VP; ++h) dwf_dx_pair(pk, h, o[h]);
         if constexpr (RED) {   // BN_e sums from the rounded dx, before the store (its last use)
           if (hok) {
-            const bool cc = (i & 1) ? cok1 : cok0;
+            const bool cc = (i & 1) ? geo.cok1 : geo.cok0;
 #pragma unroll
-            for (int h = 0; h < VP; ++h) {
-              const dw_f2 g = cc ? gate2<PACT>(ez[i][h], orr[h], pact) : zero2;
-              sg[h] += g;
-              sgx[h] = f2fma(g, f2fma(yr[i][h], ers[h], enb[h]), sgx[h]);
-            }
+            for (int h = 0; h < VP; ++h) bne.sum(h, sg[h], sgx[h], ez[i][h], dwf_dx_stored(pk, h), yr[i][h], cc);
           }
         }
-        pk.bstore(hok ? rdx : rnull, (i & 1) ? vst1 : vst0, (unsigned)(hok ? hh : 0) * rsx);
+        geo.store(pk, i, hok, hh);
       }
       // filter: dy[a] with x rows 2a-pt (tap row 0) and 2a+1-pt (1), dy[a-1] with 2a-pt (2)
       if (own) {
@@ -2430,25 +2197,7 @@ __global__ void __launch_bounds__(1024 / V, V == 4 ? 2 : 1) dw3x3_bwd_fused_s2p_
     }
   }
 
-  __syncthreads();
-  float* red = (float*)smem;
-  const int Cc = CVb * V;
-  const long part = ((long)n * tl.strips + strip) * tl.coltiles + ct;
-  auto stage = [&](const dw_f2 (&a)[VP], int qk) {
-#pragma unroll
-    for (int h = 0; h < VP; ++h) {
-      red[(qk * TB + tid) * V + 2 * h] = comp ? a[h].x : 0.f;
-      red[(qk * TB + tid) * V + 2 * h + 1] = comp ? a[h].y : 0.f;
-    }
-  };
-#pragma unroll
-  for (int k = 0; k < 9; ++k) stage(fa[k], k);
-  if constexpr (RED) {
-    stage(sg, 9);
-    stage(sgx, 10);
-  }
-  __syncthreads();
-  dw_colsum_emit<V>(red, 0, RED ? 11 : 9, TB, Cc, CVb, P, slab, gparts, part, C, cg);
+  dwf_epilogue<V, RED>((float*)smem, fa, sg, sgx, geo.comp, at, slab, gparts, at.part(tl), C);
 }
 
 extern "C" {
@@ -2485,11 +2234,11 @@ int rod_dw3x3_bwd_fused(const void* ye, const float* pro_mean, const float* pro_
   ROD_CHECK_ARG(((((uintptr_t)ye) | ((uintptr_t)dz) | ((uintptr_t)yd) | ((uintptr_t)dx)) & al) == 0,
                 "rod_dw3x3_bwd_fused: tensors must be %d-byte aligned", al + 1);
   hipStream_t s = ROD_STREAM(stream);
-  const DwTile t = dw_tile(N, A, B, C, 1, 4);
-  const dim3 grid(t.coltiles * t.cgroups, t.strips, N);
-  const BnPro pv{pro_mean, pro_rstd, pro_gamma, pro_beta, pro_act};
-  const DwBwdBn bd{bn_mean, bn_rstd, bn_gamma, bn_beta, coef, bn_act};
-  float* slab = (float*)workspace;
+  const DwFusedPlan f = dw_fused_plan(N, A, B, C, pro_mean, pro_rstd, pro_gamma, pro_beta, pro_act, bn_mean, bn_rstd,
+                                      bn_gamma, bn_beta, bn_act, coef, workspace);
+  const DwTile& t = f.t;
+  const BnPro& pv = f.pv;
+  const DwBwdBn& bd = f.bd;
   // What runs, by storage type and stride (PA: the input prologue's form; R: also BN_e's sums):
   //   bf16 stride 1   fused2, 2 channels per thread in 512-thread blocks, 3-step ring
   //   fp32 stride 1   fused2, 4 channels per thread in 256-thread blocks, 3-step ring
@@ -2510,7 +2259,7 @@ int rod_dw3x3_bwd_fused(const void* ye, const float* pro_mean, const float* pro_
     typedef decltype(tag) T;
     constexpr bool BF = sizeof(T) == 2;
     auto launch = [&](auto kern, int block, auto... tail) {
-      hipLaunchKernelGGL(kern, grid, dim3(block), 0, s, (const T*)ye, (const T*)dz, (const T*)yd, w, (T*)dx, slab,
+      hipLaunchKernelGGL(kern, f.grid, dim3(block), 0, s, (const T*)ye, (const T*)dz, (const T*)yd, w, (T*)dx, f.slab,
                          gparts, H, W, C, tail...);
     };
     const bool relu6 = bn_act == ROD_ACT_RELU6;   // BN_d's activation: inlined ReLU6, else read at run time
@@ -2534,10 +2283,7 @@ int rod_dw3x3_bwd_fused(const void* ye, const float* pro_mean, const float* pro_
       else sel_bool(gparts != nullptr, [&](auto R) { go(tag, PA, R); });
     });
   });
-  const int rc = check_launch("rod_dw3x3_bwd_fused");
-  if (rc) return rc;
-  slab_sum(slab, dw, (int)((long)N * t.strips * t.coltiles), 9L * C, s);
-  return check_launch("rod_dw3x3_bwd_fused");
+  return dw_fused_finish("rod_dw3x3_bwd_fused", f.slab, dw, N, t, C, s);
 }
 
 // PW (ABI 20): the plan the recompute kernel supports — bf16, stride 1, both BatchNorms ReLU6 (the
@@ -2567,21 +2313,15 @@ int rod_dw3x3_bwd_fused_pw(const void* ye, const float* pro_mean, const float* p
                     ((((uintptr_t)dyp) | ((uintptr_t)wt1)) & 15) == 0,
                 "rod_dw3x3_bwd_fused_pw: ye / yd / dx must be 8-byte, dyp / wt1 16-byte aligned");
   hipStream_t s = ROD_STREAM(stream);
-  const DwTile t = dw_tile(N, H, W, C, 1, 4);
-  const dim3 grid(t.coltiles * t.cgroups, t.strips, N);
-  const BnPro pv{pro_mean, pro_rstd, pro_gamma, pro_beta, pro_act};
-  const DwBwdBn bd{bn_mean, bn_rstd, bn_gamma, bn_beta, coef, bn_act};
+  const DwFusedPlan f = dw_fused_plan(N, H, W, C, pro_mean, pro_rstd, pro_gamma, pro_beta, pro_act, bn_mean, bn_rstd,
+                                      bn_gamma, bn_beta, bn_act, coef, workspace);
   const DwPw pw{(const bf16_t*)dyp, (const bf16_t*)wt1, cout};
-  float* slab = (float*)workspace;
   sel_bool(gparts != nullptr, [&](auto R) {
-    hipLaunchKernelGGL((dw3x3_bwd_fused2_kernel<bf16_t, ROD_ACT_RELU6, R, ROD_ACT_RELU6, 2, true>), grid,
+    hipLaunchKernelGGL((dw3x3_bwd_fused2_kernel<bf16_t, ROD_ACT_RELU6, R, ROD_ACT_RELU6, 2, true>), f.grid,
                        dim3(512), 0, s, (const bf16_t*)ye, (const bf16_t*)nullptr, (const bf16_t*)yd, w, (bf16_t*)dx,
-                       slab, gparts, H, W, C, t, pv, bd, pw);
+                       f.slab, gparts, H, W, C, f.t, f.pv, f.bd, pw);
   });
-  const int rc = check_launch("rod_dw3x3_bwd_fused_pw");
-  if (rc) return rc;
-  slab_sum(slab, dw, (int)((long)N * t.strips * t.coltiles), 9L * C, s);
-  return check_launch("rod_dw3x3_bwd_fused_pw");
+  return dw_fused_finish("rod_dw3x3_bwd_fused_pw", f.slab, dw, N, f.t, C, s);
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@
 // One barrier per input row: row q's tile is read, row q+1's formed, row q+2's x staged.
 #include "rod_common.h"
 #include "dw_common.h"
+#include "dwfused_common.h"
 
 namespace rod {
 
@@ -414,23 +415,15 @@ __global__ void __launch_bounds__(512, 4) dw3x3_bwd_fused_rc_kernel(
   float* xt = (float*)(wl + nct * 16 * RC_XLD);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, l16 = lane & 15;
-  const int CVb = tl.CVb * 2, P = tl.P;
-  const int p = tid / CVb, cvb = tid - (tid / CVb) * CVb;
-  int bx, strip, n;
-  xcd_block(bx, strip, n);
-  const int cg = bx % tl.cgroups, ct = bx / tl.cgroups;
-  const int Cc = CVb * V, cb = cg * Cc;
-  const int c = cb + cvb * V;
-  const int b = ct * tl.TWo + p - 1;
-  const int ci0 = 2 * b - pl;
-  const int A = ((H - 1 + pt) >> 1) + 1, B = ((W - 1 + pl) >> 1) + 1;
-  const bool comp = p >= 1 && p <= P - 2 && b < B;
-  const bool cokd = p < P && b >= 0 && b < Wo;
-  const bool cok0 = p < P && ci0 >= 0 && ci0 < W;
-  const bool cok1 = p < P && ci0 + 1 >= 0 && ci0 + 1 < W;
-  const int a0 = strip * tl.RB;
-  const int a1 = a0 + tl.RB < A ? a0 + tl.RB : A;
-  const int li = tid >= CVb ? tid - CVb : tid, ri = tid + CVb < TB ? tid + CVb : tid;
+  // the s2p kernel's thread geometry and ring without the ye loads (dwfused_common.h): ye is
+  // formed below, so of the x side only the masks apply
+  DwfS2<T, V, D, false> geo;
+  DwfPos<V> at;
+  at.init(tl);
+  geo.init(at, nullptr, dz, yd, dx, tl, H, W, C, pt, pl, Ho, Wo);
+  const int CVb = at.CVb, P = at.P, p = at.p, cvb = at.cvb, n = at.n, ct = at.ct;
+  const int Cc = CVb * V, cb = at.cg * Cc, c = at.c, li = at.li, ri = at.ri;
+  const int a0 = geo.a0, a1 = geo.a1;
   const int cbase = 2 * (ct * tl.TWo - 1) - pl;        // input column of tile pixel 0
 
   // ---- set-up: x prologue table, We rows (k zero-padded), zero k padding of the x ring ----------
@@ -453,49 +446,13 @@ __global__ void __launch_bounds__(512, 4) dw3x3_bwd_fused_rc_kernel(
   }
 
   dw_f2 wr[9][VP];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) wr[k][0] = dw_f2{w[k * C + c], w[k * C + c + 1]};
-  dw_f2 psc[VP], psh[VP], ers[VP], enb[VP];
-  const int pact = pro.act;
-  {
-    float a0_, b0_, a1_, b1_;
-    bn_pro_affine(pro, c, a0_, b0_);
-    bn_pro_affine(pro, c + 1, a1_, b1_);
-    psc[0] = dw_f2{a0_, a1_};
-    psh[0] = dw_f2{b0_, b1_};
-    ers[0] = dw_f2{pro.rstd[c], pro.rstd[c + 1]};
-    enb[0] = dw_f2{-pro.mean[c] * ers[0].x, -pro.mean[c + 1] * ers[0].y};
-  }
-  dw_f2 dsc[VP], dsh[VP], da[VP], dk1[VP], dk0[VP];
-  {
-    const int c0 = c;
-    float s0, t0, s1, t1, k10, k00, k11, k01;
-    bn_affine(bd.mean, bd.rstd, bd.gamma, bd.beta, c0, s0, t0);
-    bn_affine(bd.mean, bd.rstd, bd.gamma, bd.beta, c0 + 1, s1, t1);
-    dsc[0] = dw_f2{s0, s1};
-    dsh[0] = dw_f2{t0, t1};
-    da[0] = dw_f2{bd.coef[c0], bd.coef[c0 + 1]};
-    float m0, m1;
-    bn_bwd_k<bf16_t>(da[0].x, bd.mean[c0], bd.rstd[c0], bd.coef[C + c0], bd.coef[2 * C + c0], k10, k00, m0);
-    bn_bwd_k<bf16_t>(da[0].y, bd.mean[c0 + 1], bd.rstd[c0 + 1], bd.coef[C + c0 + 1], bd.coef[2 * C + c0 + 1], k11, k01,
-                     m1);
-    dk1[0] = dw_f2{k10, k11};
-    dk0[0] = dw_f2{k00, k01};
-  }
+  dwf_taps(w, C, c, wr);
+  DwfBnE<VP, ROD_ACT_RELU6, true> bne;
+  bne.init(pro, c);
+  DwfBnD<T, VP, ROD_ACT_RELU6> bnd;
+  bnd.init(bd, C, c);
   dw_f2 sg[VP], sgx[VP];
   sg[0] = sgx[0] = dw_f2{0.f, 0.f};
-
-  const unsigned es = sizeof(T);
-  const rsrc_t rdx = rod_rsrc(dx + (long)n * H * W * C, (unsigned)((long)H * W * C * es));
-  const rsrc_t rnull = rod_rsrc(dx + (long)n * H * W * C, 0u);
-  const rsrc_t rdz = rod_rsrc(dz + (long)n * Ho * Wo * C, (unsigned)((long)Ho * Wo * C * es));
-  const rsrc_t ryd = rod_rsrc(yd + (long)n * Ho * Wo * C, (unsigned)((long)Ho * Wo * C * es));
-  const int bc = b < 0 ? 0 : (b >= Wo ? Wo - 1 : b);
-  const int x0c = ci0 < 0 ? 0 : (ci0 >= W ? W - 1 : ci0), x1c = ci0 + 1 < 0 ? 0 : (ci0 + 1 >= W ? W - 1 : ci0 + 1);
-  const unsigned vod = (unsigned)(((long)bc * C + c) * es);
-  const unsigned vox0 = (unsigned)(((long)x0c * C + c) * es), vox1 = (unsigned)(((long)x1c * C + c) * es);
-  const unsigned vst0 = comp && cok0 ? vox0 : ROD_OOB, vst1 = comp && cok1 ? vox1 : ROD_OOB;
-  const unsigned rsx = (unsigned)(W * C * es), rsd = (unsigned)(Wo * C * es);
 
   // x staging: thread u < 2*64*KC owns (row r = u / (64*KC), pixel, k8) of a step's two x rows
   const int xr_ = tid / (RCB_NPX * KC), xrem = tid - xr_ * (RCB_NPX * KC);
@@ -545,35 +502,14 @@ __global__ void __launch_bounds__(512, 4) dw3x3_bwd_fused_rc_kernel(
   const int tp = p < P ? 2 * p : 0;
   const int yo0 = tp * ldy + cvb * V, yo1 = (tp + 1) * ldy + cvb * V;
 
-  PK rz[D], ry[D];
   bf16x8 xq;   // x of the step after next (one step of load latency cover; 128 VGPRs leave no room for two)
-  bool okd[D], okx[D][4];
-  const int dlo = a0 - 1 > 0 ? a0 - 1 : 0;
-  const int dhi = a1 - 1 < Ho - 1 ? a1 - 1 : Ho - 1;
-  auto issue = [&](int k, int q) {
-    const int a = a0 - 1 + q;
-    okd[k] = cokd && a >= dlo && a <= dhi;
-    const int ac = a < dlo ? dlo : (a > dhi ? dhi : a);
-    rz[k].bload(rdz, vod, (unsigned)ac * rsd);
-    ry[k].bload(ryd, vod, (unsigned)ac * rsd);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int hh = 2 * a - pt + (i >> 1);
-      const bool rowok = a >= a0 && (i < 2 ? a <= a1 : a < a1) && hh >= 0 && hh < H;
-      okx[k][i] = rowok && ((i & 1) ? cok1 : cok0);
-    }
-  };
-  const int nst = a1 - a0 + 2;
+  const int nst = geo.steps();
   // prologue: x of steps 0, 1 staged, steps 2, 3 in flight; ye of step 0 formed
   __syncthreads();   // the tables and the zero padding
   xstage(xload(0), 0);
   xstage(xload(1), 1);
   xq = xload(2);
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    issue(k, k);
-    __builtin_amdgcn_sched_barrier(0);
-  }
+  geo.prime();
   __syncthreads();
   form(0);
   __syncthreads();
@@ -591,12 +527,9 @@ __global__ void __launch_bounds__(512, 4) dw3x3_bwd_fused_rc_kernel(
       dw_f2 dv[VP];
       {
         dw_f2 yv[VP], zv[VP];
-        unpackv(ry[k], yv);
-        unpackv(rz[k], zv);
-        const dw_f2 z = f2fma(yv[0], dsc[0], dsh[0]);
-        const dw_f2 gg = gate2<ROD_ACT_RELU6>(z, zv[0], bd.act);
-        const dw_f2 o = f2fma(da[0], gg, f2fma(dk1[0], yv[0], dk0[0]));
-        dv[0] = okd[k] ? round2(o, T{}) : zero2;
+        unpackv(geo.ry[k], yv);
+        unpackv(geo.rz[k], zv);
+        dv[0] = geo.okd[k] ? round2(bnd.dy_of(0, yv[0], zv[0]), T{}) : zero2;
       }
       // ye at the 4 positions from the tile (slot k), the prologue, BN_e's pre-activation
       dw_f2 xv[4][VP], yr[4][VP], ez[4][VP];
@@ -610,14 +543,12 @@ __global__ void __launch_bounds__(512, 4) dw3x3_bwd_fused_rc_kernel(
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           unpackv(r4[i], yr[i]);
-          const dw_f2 z = f2fma(yr[i][0], psc[0], psh[0]);
-          const dw_f2 t = dw_f2{act_t<ROD_ACT_RELU6>(z.x), act_t<ROD_ACT_RELU6>(z.y)};
-          ez[i][0] = z;
-          xv[i][0] = okx[k][i] ? round2(t, T{}) : zero2;
+          const dw_f2 av = bne.x_of(0, yr[i][0], ez[i][0], T{});
+          xv[i][0] = geo.okx[k][i] ? av : zero2;
         }
       }
       __builtin_amdgcn_sched_barrier(0);   // the slots' reloads stay after their last reads
-      issue(k, q + D);
+      geo.issue(k, q + D);
       // the next step's ye tile, the x of the step after it staged, x two steps ahead loaded
       form((k + 1) & 1);
       xstage(xq, k);
@@ -640,18 +571,9 @@ __global__ void __launch_bounds__(512, 4) dw3x3_bwd_fused_rc_kernel(
         else if (i == 2) o = f2fma(c0, wr[5][0], c1 * wr[3][0]);
         else o = c1 * wr[4][0];
         PK pk;
-        const dw_b2 bb = __builtin_convertvector(o, dw_b2);
-        pk.v[0] = bb.x;
-        pk.v[1] = bb.y;
-        const unsigned u = __builtin_bit_cast(unsigned, bb);
-        const dw_f2 orr = dw_f2{__builtin_bit_cast(float, u << 16), __builtin_bit_cast(float, u & 0xffff0000u)};
-        if (hok) {
-          const bool cc = (i & 1) ? cok1 : cok0;
-          const dw_f2 gg = cc ? gate2<ROD_ACT_RELU6>(ez[i][0], orr, pact) : zero2;
-          sg[0] += gg;
-          sgx[0] = f2fma(gg, f2fma(yr[i][0], ers[0], enb[0]), sgx[0]);
-        }
-        pk.bstore(hok ? rdx : rnull, (i & 1) ? vst1 : vst0, (unsigned)(hok ? hh : 0) * rsx);
+        dwf_dx_pair(pk, 0, o);
+        if (hok) bne.sum(0, sg[0], sgx[0], ez[i][0], dwf_dx_stored(pk, 0), yr[i][0], (i & 1) ? geo.cok1 : geo.cok0);
+        geo.store(pk, i, hok, hh);
       }
       if (own) {
         fa[0][0] = f2fma(dv[0], xv[0][0], fa[0][0]);
@@ -671,19 +593,7 @@ __global__ void __launch_bounds__(512, 4) dw3x3_bwd_fused_rc_kernel(
     }
   }
 
-  __syncthreads();
-  float* red = (float*)smem;
-  const long part = ((long)n * tl.strips + strip) * tl.coltiles + ct;
-  auto stage = [&](const dw_f2 (&a)[VP], int qk) {
-    red[(qk * TB + tid) * V] = comp ? a[0].x : 0.f;
-    red[(qk * TB + tid) * V + 1] = comp ? a[0].y : 0.f;
-  };
-#pragma unroll
-  for (int k = 0; k < 9; ++k) stage(fa[k], k);
-  stage(sg, 9);
-  stage(sgx, 10);
-  __syncthreads();
-  dw_colsum_emit<V>(red, 0, 11, TB, Cc, CVb, P, slab, gparts, part, C, cg);
+  dwf_epilogue<V, true>((float*)smem, fa, sg, sgx, geo.comp, at, slab, gparts, at.part(tl), C);
 }
 
 inline size_t dw_bwd_rc_lds(int nct, int ldy) {
@@ -824,10 +734,7 @@ int rod_dw3x3_bwd_fused_rc(const void* x, const float* x_mean, const float* x_rs
     });
   });
   ROD_CHECK_ARG(hit, "rod_dw3x3_bwd_fused_rc: no kernel for Cin=%d nct=%d", Cin, nct);
-  const int rc = check_launch("rod_dw3x3_bwd_fused_rc");
-  if (rc) return rc;
-  slab_sum(sl, dw, (int)((long)N * t.strips * t.coltiles), 9L * C, s);
-  return check_launch("rod_dw3x3_bwd_fused_rc");
+  return dw_fused_finish("rod_dw3x3_bwd_fused_rc", sl, dw, N, t, C, s);
 }
 
 }  // extern "C"

@@ -34,6 +34,9 @@ CASES = [  # (N, H, W, C, dtype, BN_e prologue / sums, stride)
     (2, 19, 26, 12, torch.bfloat16, True, 2),
     (1, 45, 80, 96, torch.float32, False, 2),
     (1, 181, 320, 144, torch.bfloat16, True, 2),
+    # bf16 without the input BatchNorm (the PACT = -1 packed forms), both strides
+    (2, 19, 25, 12, torch.bfloat16, False, 1),
+    (2, 19, 26, 12, torch.bfloat16, False, 2),
 ]
 
 
