@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ROD_ABI_VERSION 29
+#define ROD_ABI_VERSION 30
 #define ROD_EINVAL (-1)
 
 enum { ROD_F32 = 0, ROD_BF16 = 1, ROD_I32 = 2 /* collectives only (ABI 19) */ };
@@ -89,6 +89,38 @@ int rod_augment_images(const void* src, const int64_t* src_off, const int32_t* s
 int rod_augment_boxes(const float* boxes, const int32_t* labels, const int32_t* n, const float* ref,
                       const int32_t* mode, float* boxes_out, int32_t* labels_out, int32_t* n_out, int B, int G,
                       float threshold, void* stream);
+
+/* Mosaic augmentation (ABI 30; opt-in): output image b is four tiles around center[b] = (cy, cx),
+ * 1 <= cy <= Ho, 1 <= cx <= Wo.  Tile t = 2 * (yo >= cy) + (xo >= cx) owns output pixel (yo, xo):
+ * the rectangles [0,cy)x[0,cx), [0,cy)x[cx,Wo), [cy,Ho)x[0,cx), [cy,Ho)x[cx,Wo) of th x tw pixels.
+ * Row 4 * b + t of tile_src [B][4] (an index into the S sources src / src_off [S] / src_hw [S][2],
+ * packed as above), crop [B][4][4], mode [B][4][2] and colour [B][4][3] describes tile t with the
+ * meaning of rod_augment_images.  The rectangle of a tile holds, bit for bit in either dtype, what
+ * rod_augment_images writes for that source, crop, mode and colour at Ho = th, Wo = tw: the flip is
+ * inside the tile, the resize scales are crop_h / th and crop_w / tw, the contrast mean is over
+ * the tile's th * tw pixels (summed in the partition of a th x tw image).  A tile with th == 0 or
+ * tw == 0 is empty: its table rows are never read, its source never touched; center = (Ho, Wo) is
+ * the plain single image.  Three launches per batch, as rod_augment_images.
+ * workspace: rod_mosaic_workspace(B, Ho, Wo) bytes.  out [B][Ho][Wo][3], 16-byte aligned.
+ * The tables live in device memory: the caller checks center, tile_src and the crop windows. */
+size_t rod_mosaic_workspace(int B, int Ho, int Wo);
+int rod_mosaic_images(const void* src, const int64_t* src_off, const int32_t* src_hw, const int32_t* tile_src,
+                      const int32_t* crop, const int32_t* mode, const float* colour, const int32_t* center,
+                      void* workspace, void* out, int S, int B, int Ho, int Wo, int normalize, int dtype,
+                      void* stream);
+/* Box side: boxes [S][G][4] / labels [S][G] / n [S] of the sources; ref [B][4][4] each tile's crop
+ * as a normalised box of its source.  Per output image the non-empty tiles in order t = 0..3, per
+ * tile its source's boxes in order through the chain of rod_augment_boxes in tile-normalised
+ * coordinates (resize to ref, keep iff intersection / own area with the unit box > threshold, flip
+ * when mode[b][t][0], clip to [0,1]); a kept box also has (y1 - y0) * (float)th >= min_px and
+ * (x1 - x0) * (float)tw >= min_px; then y = ((y * (float)th) + (float)oy0) / (float)Ho (three fp32
+ * operations; untouched when th == Ho) and likewise x.  Compacted in visiting order into
+ * boxes_out [B][Gout][4] / labels_out [B][Gout]; kept boxes past Gout are dropped,
+ * n_out[b] = min(kept, Gout), rows past it are zero.  One tile = rod_augment_boxes bit for bit. */
+int rod_mosaic_boxes(const float* boxes, const int32_t* labels, const int32_t* n, const int32_t* tile_src,
+                     const float* ref, const int32_t* mode, const int32_t* center, float* boxes_out,
+                     int32_t* labels_out, int32_t* n_out, int S, int B, int G, int Gout, int Ho, int Wo,
+                     float threshold, float min_px, void* stream);
 
 /* --------------------------------------------------- depthwise 3x3 (A1)
  * slim.separable_conv2d(num_outputs=None, depth_multiplier=1), padding SAME

@@ -11,6 +11,12 @@ Every source yields device tensors at the network resolution:
     img [B, H, W, 3] (uint8, or already (2/255)x-1 normalised in the compute dtype — see
     `network_input`), corner boxes fp32 [B, G, 4], labels int32 [B, G], n int32 [B]
 Synthetic BDD-shaped batches (rod.data) only with an explicit `synthetic=True`.
+
+Mosaic (opt-in, `mosaic_prob` > 0): the training sources tile four images of the batch into each
+output image (rod_mosaic_images / rod_mosaic_boxes, TrainAugmenter.sample_mosaic).  The sources
+are the batch's own images: no extra record read or decode.  From batch `mosaic_stop_step` on
+(0 = never) every image is drawn plain again, through the same entries (one tile: bit for bit
+the plain result), so the batch shapes do not change.
 """
 import glob
 import logging
@@ -25,6 +31,32 @@ from rod.data import SEED, synthetic_batch, synthetic_boxes
 GMAX = 64   # padded ground-truth boxes per training image; larger batches: next multiple
 
 log = logging.getLogger(__name__)
+
+
+def mosaic_gout(n, tile_src, center, out_hw, gmax=GMAX):
+    """Box rows per output image of a mosaic batch, by the fixed-shape rule of the training
+    sources: `gmax`, or the next multiple of 64 that holds the largest sum of the box counts of
+    an image's (non-empty) tiles' sources — nothing is ever dropped."""
+    from rod.ops import mosaic_tiles
+    rect = mosaic_tiles(center, out_hw)
+    live = (rect[:, :, 2] > 0) & (rect[:, :, 3] > 0)
+    tot = int((np.asarray(n, np.int64)[np.asarray(tile_src, np.int64)] * live).sum(1).max())
+    return max(int(gmax), -(-max(tot, 1) // GMAX) * GMAX)
+
+
+class _MosaicSwitch(object):
+    """Mosaic settings of a training source, and the switch-off from batch `stop_step` on."""
+
+    def __init__(self, aug, stop_step, start_step):
+        self.aug, self.on = aug, aug.mosaic_prob > 0
+        self.stop, self.step = int(stop_step), int(start_step)
+
+    def draw(self, src_hw, boxes, n):
+        """The next batch's tile tables (TrainAugmenter.sample_mosaic)."""
+        if self.stop > 0 and self.step >= self.stop:
+            self.aug.mosaic_prob = 0.0
+        self.step += 1
+        return self.aug.sample_mosaic(src_hw, boxes, n)
 
 
 def tfrecord_files(dataset_dir, split='train'):
@@ -55,7 +87,8 @@ class AugmentedSource(object):
     annotations, augmented per step by utils.data_pileline_tools.TrainAugmenter (random crop /
     resize / flip / colour on the device) and normalised into `dtype` (train.py:126)."""
 
-    def __init__(self, batch_size, img_size, device, dtype, seed=SEED, n_distinct=4, raw_hw=(720, 1280)):
+    def __init__(self, batch_size, img_size, device, dtype, seed=SEED, n_distinct=4, raw_hw=(720, 1280),
+                 mosaic_prob=0.0, mosaic_center=(0.25, 0.75), mosaic_min_px=2.0, mosaic_stop_step=0, start_step=0):
         from utils.data_pileline_tools import TrainAugmenter
         self.dtype = dtype
         self.raw = []
@@ -64,7 +97,9 @@ class AugmentedSource(object):
             img = torch.randint(0, 256, (batch_size, raw_hw[0], raw_hw[1], 3), dtype=torch.uint8, generator=g)
             corner, labels, n = synthetic_boxes(batch_size, seed=seed + i)
             self.raw.append((img.to(device), corner, labels, n))
-        self.aug = TrainAugmenter(img_size, seed=seed)
+        self.aug = TrainAugmenter(img_size, seed=seed, mosaic_prob=mosaic_prob, mosaic_center=mosaic_center,
+                                  mosaic_min_px=mosaic_min_px)
+        self.mosaic = _MosaicSwitch(self.aug, mosaic_stop_step, start_step)
         self.i = 0
 
     def __iter__(self):
@@ -73,6 +108,10 @@ class AugmentedSource(object):
     def __next__(self):
         img, corner, labels, n = self.raw[self.i % len(self.raw)]
         self.i += 1
+        if self.mosaic.on:
+            params = self.mosaic.draw(np.tile(np.array(img.shape[1:3], np.int32), (len(n), 1)), corner, n)
+            gout = mosaic_gout(n, params[0], params[5], self.aug.out_shape, corner.shape[1])
+            return self.aug.mosaic(img, corner, labels, n, dtype=self.dtype, params=params, gout=gout)
         return self.aug(img, corner, labels, n, dtype=self.dtype)
 
 
@@ -108,7 +147,8 @@ class TFRecordSource(object):
     augmentation kernels) is issued from the caller's thread, stream-ordered behind it."""
 
     def __init__(self, files, batch_size, img_size, device, dtype, train=True, seed=SEED, num_readers=4,
-                 verify=True, max_images=None, rank=0, world=1, gmax=GMAX, prefetch=None):
+                 verify=True, max_images=None, rank=0, world=1, gmax=GMAX, prefetch=None, mosaic_prob=0.0,
+                 mosaic_center=(0.25, 0.75), mosaic_min_px=2.0, mosaic_stop_step=0, start_step=0):
         from rod import tfrecord
         if not files:
             raise FileNotFoundError('no TFRecord files')
@@ -136,7 +176,10 @@ class TFRecordSource(object):
         self.aug = None
         if train:
             from utils.data_pileline_tools import TrainAugmenter
-            self.aug = TrainAugmenter(self.img_size, seed=seed + 1000 * self.rank)   # per-rank augmentation draws
+            self.aug = TrainAugmenter(self.img_size, seed=seed + 1000 * self.rank,   # per-rank augmentation draws
+                                      mosaic_prob=mosaic_prob, mosaic_center=mosaic_center,
+                                      mosaic_min_px=mosaic_min_px)
+        self.mosaic = _MosaicSwitch(self.aug, mosaic_stop_step, start_step) if train else None
         self.prefetch = train if prefetch is None else bool(prefetch)
         self._ahead = ThreadPoolExecutor(max_workers=1) if self.prefetch else None
         self._next_host = None
@@ -208,7 +251,10 @@ class TFRecordSource(object):
         fl = flat.numpy()
         for b, (img, _, _) in enumerate(items):
             fl[offs[b]:offs[b] + img.size] = img.reshape(-1)
-        draws = self.aug.sample(hw, boxes, n) if self.train else None
+        if self.train and self.mosaic.on:
+            draws = self.mosaic.draw(hw, boxes, n)
+        else:
+            draws = self.aug.sample(hw, boxes, n) if self.train else None
         up = None
         if self._copy_stream is not None:   # the upload, on the copy stream (see __init__)
             with torch.cuda.stream(self._copy_stream):
@@ -229,6 +275,14 @@ class TFRecordSource(object):
             src.record_stream(cur)   # the copy stream's allocation is used on this stream
         else:
             src = flat.to(self.device, non_blocking=True)
+        if self.train and self.mosaic.on:
+            tile_src, crop, ref, mode, colour, center = draws
+            x = ops.mosaic_images(src, tile_src, crop, mode, colour, center, self.img_size, dtype=self.dtype,
+                                  normalize=True, src_hw=hw, src_off=offs)
+            bo, lo, no = ops.mosaic_boxes(boxes, labels, n, tile_src, ref, mode, center, self.img_size,
+                                          gout=mosaic_gout(n, tile_src, center, self.img_size, self.gmax or GMAX),
+                                          threshold=0.3, min_px=self.aug.mosaic_min_px)
+            return x, bo, lo, no
         if self.train:
             crop, ref, mode, colour = draws
             x = ops.augment_images(src, crop, mode, colour, self.img_size, dtype=self.dtype, normalize=True,
@@ -252,13 +306,20 @@ class TFRecordSource(object):
 
 
 def make_source(dataset_dir, batch_size, img_size, device, split='train', seed=SEED, augment_dtype=None,
-                synthetic=False, dtype=torch.float32, num_readers=4, max_images=None, rank=0, world=1):
+                synthetic=False, dtype=torch.float32, num_readers=4, max_images=None, rank=0, world=1,
+                mosaic_prob=0.0, mosaic_center=(0.25, 0.75), mosaic_min_px=2.0, mosaic_stop_step=0, start_step=0):
     """augment_dtype: training batches go through the GPU augmentation pipeline and come out
     normalised in this dtype; None = network-resolution uint8 batches (eval / predict / bench).
     synthetic: run on synthetic BDD-shaped batches (rod.data) — only when asked for explicitly;
     a missing dataset is an error, as in the reference (its reader fails on an empty pattern).
     rank / world: data parallel — TFRecords are read as disjoint per-rank slices of one shared
-    shuffle; synthetic sources draw per-rank batches (seed + 1000 * rank)."""
+    shuffle; synthetic sources draw per-rank batches (seed + 1000 * rank).
+    mosaic_*: mosaic augmentation of the augmented training batches (module docstring); start_step:
+    the step the run resumes from, which mosaic_stop_step counts against."""
+    mosaic = dict(mosaic_prob=mosaic_prob, mosaic_center=mosaic_center, mosaic_min_px=mosaic_min_px,
+                  mosaic_stop_step=mosaic_stop_step, start_step=start_step)
+    if mosaic_prob > 0 and augment_dtype is None:
+        raise ValueError('mosaic_prob > 0 needs the augmented training source (augment_dtype)')
     if synthetic:
         log.warning('--synthetic: using synthetic BDD-shaped batches (rod.data), not %r', dataset_dir)
     else:
@@ -268,10 +329,10 @@ def make_source(dataset_dir, batch_size, img_size, device, split='train', seed=S
             train = augment_dtype is not None
             return TFRecordSource(files, batch_size, img_size, torch.device(device),
                                   augment_dtype if train else dtype, train=train, seed=seed, num_readers=num_readers,
-                                  max_images=max_images, rank=rank, world=world)
+                                  max_images=max_images, rank=rank, world=world, **(mosaic if train else {}))
         raise FileNotFoundError('no bdd100k_%s_*.tfrecord under %r (pass --synthetic to run on synthetic '
                                 'BDD-shaped batches)' % (split, dataset_dir))
     seed = seed + 1000 * rank
     if augment_dtype is not None:
-        return AugmentedSource(batch_size, img_size, device, augment_dtype, seed)
+        return AugmentedSource(batch_size, img_size, device, augment_dtype, seed, **mosaic)
     return SyntheticSource(batch_size, img_size, device, seed)

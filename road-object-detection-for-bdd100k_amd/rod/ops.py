@@ -287,6 +287,96 @@ def augment_boxes(boxes, labels, n, ref, mode=None, threshold=0.3):
     return bo, lo, no
 
 
+def mosaic_tiles(center, out_hw):
+    """[B, 4, 4] (oy0, ox0, th, tw) of the four tiles around center [B, 2] = (cy, cx): tile
+    t = 2 * (yo >= cy) + (xo >= cx) owns output pixel (yo, xo) (include/rod.h, ABI 30)."""
+    c = np.asarray(center, np.int64).reshape(-1, 2)
+    Ho, Wo = int(out_hw[0]), int(out_hw[1])
+    cy, cx, z = c[:, 0], c[:, 1], np.zeros(len(c), np.int64)
+    return np.stack([np.stack([z, z, cy, cx], 1), np.stack([z, cx, cy, Wo - cx], 1),
+                     np.stack([cy, z, Ho - cy, cx], 1), np.stack([cy, cx, Ho - cy, Wo - cx], 1)], 1)
+
+
+def _mosaic_tables(name, tile_src, center, out_hw, S):
+    """center and tile_src of a mosaic batch, checked: center inside the canvas, the source index
+    of every non-empty tile in [0, S).  Returns (tile_src [B, 4], center [B, 2], live [B, 4])."""
+    Ho, Wo = int(out_hw[0]), int(out_hw[1])
+    center = np.asarray(center, np.int32).reshape(-1, 2)
+    B = len(center)
+    tile_src = np.asarray(tile_src, np.int32).reshape(B, 4)
+    if B == 0 or S <= 0:
+        raise ValueError('%s: empty batch' % name)
+    if (center < 1).any() or (center[:, 0] > Ho).any() or (center[:, 1] > Wo).any():
+        raise ValueError('%s: center outside [1, Ho] x [1, Wo]' % name)
+    rect = mosaic_tiles(center, out_hw)
+    live = (rect[:, :, 2] > 0) & (rect[:, :, 3] > 0)
+    if ((tile_src < 0) | (tile_src >= S))[live].any():
+        raise ValueError('%s: tile_src outside [0, %d)' % (name, S))
+    return tile_src, center, live
+
+
+def mosaic_images(src, tile_src, crop, mode, colour, center, out_hw, dtype=torch.float32, normalize=False,
+                  src_hw=None, src_off=None):
+    """rod_mosaic_images: per output image four tiles around center [B, 2] = (cy, cx), each the
+    rod_augment_images chain of source tile_src [B, 4] with crop [B, 4, 4], mode [B, 4, 2], colour
+    [B, 4, 3] at the tile's size, bit for bit.  src as in augment_images (S sources); the tables are
+    host arrays.  Rows of empty tiles (center on the canvas edge) are ignored."""
+    dev = src.device
+    if src_hw is None:
+        S, H, W, _ = src.shape
+        src_hw = np.tile(np.array([H, W], np.int32), (S, 1))
+        src_off = np.arange(S, dtype=np.int64) * (H * W * 3)
+    S = len(src_hw)
+    Ho, Wo = int(out_hw[0]), int(out_hw[1])
+    tile_src, center, live = _mosaic_tables('mosaic_images', tile_src, center, out_hw, S)
+    B = len(center)
+    crop = np.asarray(crop, np.int32).reshape(B, 4, 4)
+    hw = np.asarray(src_hw, np.int64).reshape(S, 2)
+    c, thw = crop[live].astype(np.int64), hw[tile_src[live]]
+    if (c[:, :2] < 0).any() or (c[:, 2:] <= 0).any() or (c[:, 0] + c[:, 2] > thw[:, 0]).any() or \
+            (c[:, 1] + c[:, 3] > thw[:, 1]).any():
+        raise ValueError('mosaic_images: crop window outside the source image')
+    if int((hw[:, 0] * hw[:, 1] * 3).max()) >= 2 ** 31:
+        raise ValueError('mosaic_images: a source image exceeds 2 GiB')
+    if int((np.asarray(src_off, np.int64) + hw[:, 0] * hw[:, 1] * 3).max()) > src.numel():
+        raise ValueError('mosaic_images: source offsets exceed the buffer')
+    out = torch.empty((B, Ho, Wo, 3), dtype=dtype, device=dev)
+    ws = workspace(_abi.query('rod_mosaic_workspace', B, Ho, Wo), dev)
+    _abi.call('rod_mosaic_images', src, _device_i(src_off, dev, torch.int64), _device_i(src_hw, dev, torch.int32),
+              _device_i(tile_src, dev, torch.int32), _device_i(crop, dev, torch.int32),
+              _device_i(np.asarray(mode, np.int32).reshape(B, 4, 2), dev, torch.int32),
+              _device_i(np.asarray(colour, np.float32).reshape(B, 4, 3), dev, torch.float32),
+              _device_i(center, dev, torch.int32), ws, out, S, B, Ho, Wo, int(bool(normalize)), dtcode(out),
+              stream())
+    return out
+
+
+def mosaic_boxes(boxes, labels, n, tile_src, ref, mode, center, out_hw, gout=None, threshold=0.3, min_px=0.0):
+    """rod_mosaic_boxes: the sources' boxes [S, G, 4] / labels [S, G] / n [S] (device tensors or host
+    arrays) through the rod_augment_boxes chain per tile (ref [B, 4, 4], mode [B, 4, 2]), a size floor
+    of min_px tile pixels, and the map onto the canvas; compacted in tile order into gout (default G)
+    rows per output image.  Returns device (boxes, labels, n), zero-padded past n."""
+    dev = boxes.device if torch.is_tensor(boxes) else torch.device('cuda')
+    b = boxes if torch.is_tensor(boxes) else _device_i(np.asarray(boxes, np.float32), dev, torch.float32)
+    lab = labels if torch.is_tensor(labels) else _device_i(np.asarray(labels, np.int32), dev, torch.int32)
+    nn = n if torch.is_tensor(n) else _device_i(np.asarray(n, np.int32), dev, torch.int32)
+    S, G = b.shape[0], b.shape[1]
+    tile_src, center, _ = _mosaic_tables('mosaic_boxes', tile_src, center, out_hw, S)
+    B = len(center)
+    gout = G if gout is None else int(gout)
+    if gout <= 0:
+        raise ValueError('mosaic_boxes: gout must be positive')
+    bo = torch.empty((B, gout, 4), dtype=torch.float32, device=dev)
+    lo = torch.empty((B, gout), dtype=torch.int32, device=dev)
+    no = torch.empty((B,), dtype=torch.int32, device=dev)
+    _abi.call('rod_mosaic_boxes', b.contiguous(), lab.contiguous(), nn, _device_i(tile_src, dev, torch.int32),
+              _device_i(np.asarray(ref, np.float32).reshape(B, 4, 4), dev, torch.float32),
+              _device_i(np.asarray(mode, np.int32).reshape(B, 4, 2), dev, torch.int32),
+              _device_i(center, dev, torch.int32), bo, lo, no, S, B, G, gout, int(out_hw[0]), int(out_hw[1]),
+              float(threshold), float(min_px), stream())
+    return bo, lo, no
+
+
 def cast(x: torch.Tensor, dtype) -> torch.Tensor:
     if x.dtype == dtype:
         return x

@@ -67,6 +67,10 @@ def cost(name, a):
         # written network input + one uint8 sample per output value read (the crop is resampled)
         B, Ho, Wo, dt = a[8], a[9], a[10], a[12]
         return (_ES[dt] + 1) * B * Ho * Wo * 3, 0
+    if name == "rod_mosaic_images":
+        # ABI 30: the same output pixels as rod_augment_images, whatever the tiling
+        B, Ho, Wo, dt = a[11], a[12], a[13], a[15]
+        return (_ES[dt] + 1) * B * Ho * Wo * 3, 0
     if name == "rod_dw3x3_fwd":
         N, H, W, C, Ho, Wo, dt = a[9], a[10], a[11], a[12], a[16], a[17], a[18]
         es = _ES[dt]

@@ -28,6 +28,11 @@ the trainable variables (tf.train.ExponentialMovingAverage; --ema_warmup True ap
 num_updates rule min(d, (1 + step) / (10 + step))), updated inside the optimiser's launch, under
 --hip_graph too.  It is saved with every checkpoint and restored on resume; evaluate.py and
 predict.py read it with --use_ema True.
+
+Mosaic augmentation (with --augment): --mosaic_prob p (default 0 = off) tiles, with probability p per
+image, four images of the batch around a random centre (--mosaic_center lo,hi as fractions of the
+image size, default 0.25,0.75) on the GPU; boxes under --mosaic_min_px tile pixels are dropped, and
+--mosaic_stop_step N draws plain images again from step N on (0 = never).
 """
 import argparse
 import json
@@ -51,6 +56,15 @@ def str2bool(v):
 
 def none_or_str(v):
     return None if v in (None, '', 'None', 'none') else v
+
+
+def center_range(v):
+    """'lo,hi' -> (lo, hi)"""
+    try:
+        lo, hi = (float(t) for t in str(v).split(','))
+    except ValueError:
+        raise argparse.ArgumentTypeError('expected lo,hi, got %r' % (v,))
+    return lo, hi
 
 
 def parse(argv=None):
@@ -125,7 +139,27 @@ def parse(argv=None):
     ap.add_argument('--ema_warmup', type=str2bool, default=True,
                     help="the average's decay is min(ema_decay, (1 + step) / (10 + step)) "
                          '(tf.train.ExponentialMovingAverage with num_updates); False: ema_decay from the first step')
+    # input-side addition (neutral by default: one crop per image, every draw as before)
+    ap.add_argument('--mosaic_prob', type=float, default=0.0,
+                    help='probability, in [0, 1], that a training image is a mosaic of four images of its batch '
+                         '(0 = off); needs --augment')
+    ap.add_argument('--mosaic_center', type=center_range, default=(0.25, 0.75),
+                    help='lo,hi: the mosaic centre is drawn uniformly in [lo, hi] of the image height and width')
+    ap.add_argument('--mosaic_min_px', type=float, default=2.0,
+                    help='mosaic: drop boxes whose clipped height or width is under this many tile pixels')
+    ap.add_argument('--mosaic_stop_step', type=int, default=0,
+                    help='mosaic: off from this step on, for a clean final phase (0 = never)')
     F = ap.parse_args(argv)
+    if not 0.0 <= F.mosaic_prob <= 1.0:       # (a NaN fails both comparisons)
+        ap.error('--mosaic_prob must be in [0, 1], got %r' % F.mosaic_prob)
+    if not 0.0 <= F.mosaic_center[0] <= F.mosaic_center[1] <= 1.0:
+        ap.error('--mosaic_center needs 0 <= lo <= hi <= 1, got %r' % (F.mosaic_center,))
+    if not (0.0 <= F.mosaic_min_px < float('inf')):
+        ap.error('--mosaic_min_px must be finite and >= 0, got %r' % F.mosaic_min_px)
+    if F.mosaic_stop_step < 0:
+        ap.error('--mosaic_stop_step must be >= 0, got %r' % F.mosaic_stop_step)
+    if F.mosaic_prob > 0 and not F.augment:
+        ap.error('--mosaic_prob needs --augment True: mosaic is part of the GPU augmentation')
     if not 0.0 <= F.ema_decay < 1.0:       # (a NaN fails both comparisons)
         ap.error('--ema_decay must be in [0, 1), got %r' % F.ema_decay)
     loc_given = F.loc_loss_weight is not None
@@ -288,7 +322,13 @@ def main(argv=None):
     logger.info('Building data pileline, using dataset---%s' % 'bdd100k_train')
     source = make_source(F.dataset_dir, F.batch_size, config.img_size, dev, seed=F.seed,
                          augment_dtype=dtype if F.augment else None, synthetic=F.synthetic, dtype=dtype,
-                         num_readers=F.num_readers, rank=rank, world=world)
+                         num_readers=F.num_readers, rank=rank, world=world, mosaic_prob=F.mosaic_prob,
+                         mosaic_center=F.mosaic_center, mosaic_min_px=F.mosaic_min_px,
+                         mosaic_stop_step=F.mosaic_stop_step, start_step=step0)
+    if F.mosaic_prob > 0:
+        logger.info('Mosaic augmentation: probability %g, centre in [%g, %g]%s' % (
+            (F.mosaic_prob,) + F.mosaic_center +
+            (', off from step %d' % F.mosaic_stop_step if F.mosaic_stop_step else '',)))
 
     os.makedirs(F.summary_dir, exist_ok=True)
     summ = open(os.path.join(F.summary_dir, 'train_rank%d.jsonl' % rank), 'a') if rank == 0 else None

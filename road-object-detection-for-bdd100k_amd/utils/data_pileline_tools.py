@@ -26,13 +26,31 @@ class TrainAugmenter(object):
 
     and, fused when `dtype` is given, train.py:126 `(2/255) * imgs - 1` cast to DTYPE.
     `seed` drives the per-image draws (numpy); the colour magnitudes come from Python's
-    `random`, once per augmenter, as the reference draws them once per graph."""
+    `random`, once per augmenter, as the reference draws them once per graph.
 
-    def __init__(self, out_shape, seed=0, py_random=None):
+    Mosaic (opt-in, mosaic_prob > 0; rod_mosaic_images / rod_mosaic_boxes): with that probability
+    output image b becomes four tiles around a centre drawn on the integers of
+    [lo * size, hi * size] (mosaic_center = (lo, hi), clamped to [1, size - 1]) — tile 0 image b
+    itself, tiles 1-3 three other images of the same batch — each tile with its own crop, flip
+    and colour draw by the rules above; boxes smaller than mosaic_min_px tile pixels are dropped.
+    Everything mosaic adds is drawn from a second generator, so the draws of tile 0 are the
+    sequence a plain augmenter of the same seed draws."""
+
+    def __init__(self, out_shape, seed=0, py_random=None, mosaic_prob=0.0, mosaic_center=(0.25, 0.75),
+                 mosaic_min_px=2.0):
         import random
         self.out_shape = tuple(out_shape)
         self.rng = np.random.default_rng(seed)
         self.color = process.ColorDistorter(py_random if py_random is not None else random.Random(seed))
+        lo, hi = (float(v) for v in mosaic_center)
+        if not 0.0 <= float(mosaic_prob) <= 1.0:       # (a NaN fails both comparisons)
+            raise ValueError('mosaic_prob must be in [0, 1], got %r' % (mosaic_prob,))
+        if not 0.0 <= lo <= hi <= 1.0:
+            raise ValueError('mosaic_center must be 0 <= lo <= hi <= 1, got %r' % (mosaic_center,))
+        if not 0.0 <= float(mosaic_min_px) < float('inf'):
+            raise ValueError('mosaic_min_px must be finite and >= 0, got %r' % (mosaic_min_px,))
+        self.mosaic_prob, self.mosaic_center, self.mosaic_min_px = float(mosaic_prob), (lo, hi), float(mosaic_min_px)
+        self.mosaic_rng = np.random.default_rng([int(seed) & 0xFFFFFFFF, 0x6D6F7361])   # 'mosa'
 
     def sample(self, src_hw, boxes, n):
         """Per-image parameters: crop [B,4], distort_bbox [B,4], mode [B,2], colour [B,3]."""
@@ -49,6 +67,62 @@ class TrainAugmenter(object):
             mode[b, 0] = int(self.rng.uniform(0, 1) < .5)       # random_flip_left_right
             mode[b, 1], colour[b] = self.color.sample(self.rng)  # apply_with_random_selector
         return crop, ref, mode, colour
+
+    def _draw(self, rng, H, W, boxes):
+        """One image's crop, distort_bbox, flip and colour draw from `rng`, in sample()'s order."""
+        crop, ref = process.distorted_bounding_box_crop(rng, H, W, boxes, min_object_covered=0.4,
+                                                        aspect_ratio_range=(0.6, 1.67))
+        flip = int(rng.uniform(0, 1) < .5)
+        ordering, colour = self.color.sample(rng)
+        return crop, ref, (flip, ordering), colour
+
+    def _center(self, size):
+        lo, hi = self.mosaic_center
+        a, b = int(np.ceil(lo * size)), int(np.floor(hi * size))
+        c = int(self.mosaic_rng.integers(a, b + 1)) if b >= a else int(round(.5 * (lo + hi) * size))
+        return min(max(c, 1), max(size - 1, 1))
+
+    def sample_mosaic(self, src_hw, boxes, n):
+        """Tile tables of a batch: tile_src [B,4], crop [B,4,4], distort_bbox [B,4,4], mode [B,4,2],
+        colour [B,4,3], center [B,2].  Tile 0 of image b is image b with sample()'s draws (from the
+        same generator, in the same order); a non-mosaic image has center = out_shape, i.e. tile 0
+        alone.  The other tiles' rows of such an image repeat tile 0's and are never read."""
+        B = len(src_hw)
+        Ho, Wo = self.out_shape
+        crop0, ref0, mode0, colour0 = self.sample(src_hw, boxes, n)
+        tile_src = np.repeat(np.arange(B, dtype=np.int32)[:, None], 4, 1)
+        crop, ref = np.repeat(crop0[:, None], 4, 1), np.repeat(ref0[:, None], 4, 1)
+        mode, colour = np.repeat(mode0[:, None], 4, 1), np.repeat(colour0[:, None], 4, 1)
+        center = np.tile(np.array([Ho, Wo], np.int32), (B, 1))
+        rng = self.mosaic_rng
+        for b in range(B):
+            if not (self.mosaic_prob > 0 and Ho > 1 and Wo > 1 and rng.uniform(0, 1) < self.mosaic_prob):
+                continue
+            center[b] = self._center(Ho), self._center(Wo)
+            if B >= 4:      # three other images, distinct
+                others = np.delete(np.arange(B), b)
+                tile_src[b, 1:] = rng.choice(others, 3, replace=False)
+            else:           # too few for that: any image of the batch, with replacement
+                tile_src[b, 1:] = rng.integers(0, B, 3)
+            for t in range(1, 4):
+                s = int(tile_src[b, t])
+                crop[b, t], ref[b, t], mode[b, t], colour[b, t] = self._draw(
+                    rng, int(src_hw[s][0]), int(src_hw[s][1]), boxes[s][:int(n[s])])
+        return tile_src, crop, ref, mode, colour, center
+
+    def mosaic(self, images, boxes, labels, n, dtype=None, params=None, gout=None):
+        """__call__ through the mosaic entries (images [B, H, W, 3] are the batch's own sources)."""
+        boxes = np.asarray(boxes, np.float32)
+        B, H, W, _ = images.shape
+        src_hw = np.tile(np.array([H, W], np.int32), (B, 1))
+        tile_src, crop, ref, mode, colour, center = params if params is not None else \
+            self.sample_mosaic(src_hw, boxes, n)
+        img = ops.mosaic_images(images, tile_src, crop, mode, colour, center, self.out_shape,
+                                dtype=dtype if dtype is not None else torch.float32, normalize=dtype is not None)
+        bo, lo, no = ops.mosaic_boxes(boxes, labels, n, tile_src, ref, mode, center, self.out_shape, gout=gout,
+                                      threshold=process.BBOX_CROP_OVERLAP, min_px=self.mosaic_min_px)
+        self.last_params = (tile_src, crop, ref, mode, colour, center)
+        return img, bo, lo, no
 
     def __call__(self, images, boxes, labels, n, dtype=None, params=None):
         """images: uint8 [B, H, W, 3] device tensor; boxes [B, G, 4] / labels [B, G] / n [B] as
