@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ROD_ABI_VERSION 30
+#define ROD_ABI_VERSION 31
 #define ROD_EINVAL (-1)
 
 enum { ROD_F32 = 0, ROD_BF16 = 1, ROD_I32 = 2 /* collectives only (ABI 19) */ };
@@ -821,6 +821,41 @@ int rod_match_detections(const float* det_scores, const float* det_boxes, const 
                          const float* gt_boxes, const uint8_t* gt_difficult, const int32_t* gt_count,
                          const float* thresholds, int B, int C, int N, int G, int T, int first_label,
                          int32_t* tp_mask, int32_t* fp_mask, int32_t* n_gt, void* stream);
+
+/* ------------------------------------------------ evaluation: TP/FP by object-area range (ABI 31; opt-in)
+ * rod_match_detections reported for R area ranges in the same single launch: the inputs of
+ * rod_match_detections plus area_ranges, a DEVICE fp32 array [R,2] of (lo, hi) pairs in the boxes'
+ * own (normalised) area units.  Outputs tp_mask / fp_mask [R,B,C,N] (bit t = threshold t) and
+ * n_gt [R,B,C].
+ *   area(box)   = (ymax - ymin) * (xmax - xmin), one fp32 subtraction pair and one fp32 multiply —
+ *                 the area_g / area_det expression of the IoU above, in the same order.
+ *   in_r(a)     = !(a < lo_r) && !(a >= hi_r): lo inclusive, hi exclusive, a NaN area is inside
+ *                 every range; lo = -inf and hi = +inf are legal.
+ * Range-independent, exactly as in rod_match_detections: idx_i (first argmax; all 0: ground truth
+ * 0), jac_i, nd_i, match_it = jac_i,idx > thresholds[t], and first[idx][t] = the first i in
+ * score order with idx_i == idx && nd_i && match_it.  Then, for every range r:
+ *   n_gt[r,b,c] the number of j < g with label_j == label, not difficult and in_r(area(gt_j)).
+ *   g == 0      tp = 0 and fp = in_r(area(det_i)) in all T bits.
+ *   !nd_i       tp = fp = 0 in every bit (the difficult rule, whatever the IoU).
+ *   match_it    ground truth idx_i outside the range (!in_r(area(gt_idx))): tp = fp = 0 — the
+ *               detection is matched to ignored ground truth; inside it: tp = (first[idx][t] == i),
+ *               fp = !tp.
+ *   !match_it   tp = 0, fp = in_r(area(det_i)): an unmatched detection is an FP only of the
+ *               ranges its own area lies in.
+ * With R = 1 and the range (-inf, +inf) the outputs equal rod_match_detections' bit for bit for
+ * every input whose box areas are not +inf (+inf >= hi excludes such a box from every range).
+ * Not pycocotools' rule: a detection competes for the reference's argmax ground truth whether
+ * that box is ignored in the range or not, where pycocotools re-matches toward non-ignored
+ * ground truth; and AP over these masks is this project's VOC value, not the COCO metric.
+ * One workgroup per (b, c) as above; the stage phase keeps one byte per ground-truth row in LDS
+ * (bit r = in range r; + G bytes) and only the final store loops over r.
+ * Limits, checked before any HIP call: those of rod_match_detections, 1 <= R <= 8, area_ranges
+ * != NULL.  No workspace, no allocation, no host synchronisation: capturable. */
+int rod_match_detections_area(const float* det_scores, const float* det_boxes, const int32_t* gt_labels,
+                              const float* gt_boxes, const uint8_t* gt_difficult, const int32_t* gt_count,
+                              const float* thresholds, const float* area_ranges, int B, int C, int N, int G,
+                              int T, int R, int first_label, int32_t* tp_mask, int32_t* fp_mask,
+                              int32_t* n_gt, void* stream);
 
 /* ------------------------------------------------ optimiser (A14)
  * Plain SGD with clip by value (net_tools.py:645-651):

@@ -12,8 +12,11 @@ per batch; --ap_iou_sweep evaluates AP at several matching IoU thresholds from t
 per batch.  At every threshold the rule is the reference's own matching rule (bboxes_matching:
 first argmax of IoU over same-label boxes, strict comparison, one TP per ground truth), not
 pycocotools' rule, and AP is this project's VOC12 area / VOC07 11-point value — the mean over the
-sweep is a mean of those, not the COCO metric.  Without the new flags the run, its printout and
-eval.json are today's.
+sweep is a mean of those, not the COCO metric.  --ap_area_ranges also reports AP and recall by
+object-size range from that same launch (rod_match_detections_area): ground truth outside a range
+is ignored, a detection matched to it is neither TP nor FP, an unmatched detection is an FP only
+of the ranges its own area lies in — again on the reference's argmax, not pycocotools'
+re-matching.  Without the new flags the run, its printout and eval.json are today's.
 """
 import argparse
 import math
@@ -73,6 +76,17 @@ def parse(argv=None):
                          "reference's matching rule (not pycocotools' rule) and AP stays this project's VOC12 area "
                          '/ VOC07 11-point value; at most %d distinct thresholds with --matching_threshold'
                          % MAX_THRESHOLDS)
+    ap.add_argument('--ap_area_ranges', default='',
+                    help="also report AP and recall by object-size range: 'coco' = %s, or a comma list "
+                         "name:lo:hi in pixels^2 of the --ap_area_image_size frame (lo inclusive, hi exclusive, hi "
+                         "may be inf; unique names, at most %d).  Implies --match_on device.  Ground truth outside "
+                         "a range is ignored and a detection matched to it counts as neither TP nor FP, but a "
+                         "detection still competes for the reference's argmax ground truth whether that box is "
+                         "ignored or not (pycocotools re-matches toward non-ignored ground truth), and AP stays "
+                         "this project's VOC value, not the COCO metric" % (COCO_AREA_RANGES, MAX_AREA_RANGES))
+    ap.add_argument('--ap_area_image_size', default='720,1280',
+                    help='H,W of the frame the pixel bounds of --ap_area_ranges refer to (the BDD100K frame): the '
+                         'boxes are normalised, so an object lands in the same range at any network resolution')
     ap.add_argument('--use_ema', type=str2bool, default=False,
                     help='evaluate the averaged weights the checkpoint holds (train.py --ema_decay) in place of '
                          'the variables; an error if it holds none')
@@ -81,9 +95,16 @@ def parse(argv=None):
         F.sweep_thresholds = parse_iou_sweep(F.ap_iou_sweep)
     except ValueError as e:
         ap.error('--ap_iou_sweep: %s' % e)
-    if F.sweep_thresholds.size:
+    try:
+        F.area_names, F.area_ranges_px = parse_area_ranges(F.ap_area_ranges)
+        F.area_image_size = parse_image_size(F.ap_area_image_size)
+    except ValueError as e:
+        ap.error('--ap_area_ranges / --ap_area_image_size: %s' % e)
+    F.area_ranges = area_ranges_normalised(F.area_ranges_px, F.area_image_size)
+    if F.sweep_thresholds.size or F.area_names:
         if F.match_on == 'host':
-            ap.error('--ap_iou_sweep needs --match_on device (the host loop matches at one threshold)')
+            ap.error('--ap_iou_sweep and --ap_area_ranges need --match_on device (the host loop matches at one '
+                     'threshold and knows no ignored ground truth)')
         F.match_on = 'device'
     elif F.match_on is None:
         F.match_on = 'host'
@@ -115,6 +136,49 @@ def parse_iou_sweep(text):
         if v not in vals:
             vals.append(v)
     return np.array(vals, np.float32)
+
+
+MAX_AREA_RANGES = 8   # bits of rod_match_detections_area's per-row range byte (include/rod.h)
+COCO_AREA_RANGES = 'all:0:inf,small:0:1024,medium:1024:9216,large:9216:inf'   # 32^2 and 96^2 pixels
+
+
+def parse_area_ranges(text):
+    """'' -> no ranges; 'coco' -> COCO_AREA_RANGES; else a comma list name:lo:hi (pixels^2, lo <
+    hi, hi may be inf, unique names, at most MAX_AREA_RANGES).  ([name], float64 [n, 2])."""
+    text = text.strip()
+    if not text:
+        return [], np.zeros((0, 2), np.float64)
+    names, px = [], []
+    for tok in (COCO_AREA_RANGES if text == 'coco' else text).split(','):
+        parts = tok.split(':')
+        if len(parts) != 3 or not parts[0].strip():
+            raise ValueError('range %r is not name:lo:hi' % tok)
+        name, lo, hi = parts[0].strip(), float(parts[1]), float(parts[2])   # ValueError on a malformed number
+        if name in names:
+            raise ValueError('range name %r is given twice' % name)
+        if not lo < hi:      # rejects NaN bounds too
+            raise ValueError('range %r: lo must be below hi' % tok)
+        names.append(name)
+        px.append((lo, hi))
+    if len(names) > MAX_AREA_RANGES:
+        raise ValueError('%d ranges, at most %d' % (len(names), MAX_AREA_RANGES))
+    return names, np.array(px, np.float64)
+
+
+def parse_image_size(text):
+    parts = text.split(',')
+    if len(parts) != 2:
+        raise ValueError('image size %r is not H,W' % text)
+    h, w = int(parts[0]), int(parts[1])
+    if h <= 0 or w <= 0:
+        raise ValueError('image size %r is not positive' % text)
+    return h, w
+
+
+def area_ranges_normalised(px, image_size):
+    """Pixel^2 bounds [n, 2] -> the float32 bounds in the boxes' normalised area units."""
+    h, w = image_size
+    return np.float32(np.float64(px) / (h * w)).reshape(-1, 2)
 
 
 def iou_key(t):
@@ -175,10 +239,14 @@ def main(argv=None):
     state = None
     classes = list(range(1, config.total_obj_n))
     on_device = F.match_on == 'device'
+    by_area = bool(F.area_names)
     if on_device:
         from rod import ops
+        # by area: slot 0 is (-inf, +inf), whose masks are rod_match_detections' own and feed today's
+        # outputs; the named ranges follow
+        slots = np.concatenate([np.array([[-np.inf, np.inf]], np.float32), F.area_ranges]) if by_area else None
         acc = tfe.SweepTPFP(F.match_thresholds, len(classes), num_batches * F.batch_size, F.keep_top_k, dev,
-                            first_label=classes[0])
+                            first_label=classes[0], area_ranges=slots)
     start = time.time()
     with torch.no_grad():
         for _ in range(num_batches):
@@ -193,6 +261,10 @@ def main(argv=None):
                     probs, boxes, select_threshold=F.select_threshold, nms_threshold=F.nms_threshold,
                     top_k=F.select_top_k, keep_top_k=F.keep_top_k, nms_method=F.nms_method,
                     soft_nms_sigma=F.soft_nms_sigma, soft_nms_min_score=F.soft_nms_min_score)
+                if by_area:
+                    acc.update(pscores, *match_by_area(ops, pscores, pboxes, glabels, gboxes, gn, acc.thresholds_dev,
+                                                       acc.area_ranges_dev, classes[0]))
+                    continue
                 acc.update(pscores, *ops.match_detections(pscores, pboxes, glabels, gboxes, gn, acc.thresholds_dev,
                                                           first_label=classes[0]))
                 continue
@@ -210,7 +282,9 @@ def main(argv=None):
     aps07, aps12 = {}, {}
     if on_device:
         per_threshold = acc.value()       # the run's one device -> host copy
-        by07, by12 = acc.average_precisions(per_threshold)
+        if by_area:
+            per_range, per_threshold = per_threshold[1:], per_threshold[0]
+        by07, by12 = tfe.sweep_average_precisions(per_threshold)   # all-range: AP 0, not None, without ground truth
     for c in classes:
         prec, rec = tfe.precision_recall(*(per_threshold[0][c] if on_device else state[c].value()))
         aps07[c] = tfe.average_precision_voc07(prec, rec)
@@ -239,6 +313,8 @@ def main(argv=None):
                                                                  extra['mAP_VOC12_by_iou'][k]))
         print('IoU sweep mean (reference matching rule, VOC AP)  AP_VOC07/mAP[%s]  AP_VOC12/mAP[%s]'
               % (extra['mAP_VOC07_sweep'], extra['mAP_VOC12_sweep']))
+    if by_area:
+        extra.update(area_outputs(F, tfe, per_range, *acc.average_precisions(per_range)))
     elapsed = time.time() - start
     print('Time spent : %.3f seconds.' % elapsed)
     print('Time spent per BATCH: %.3f seconds.' % (elapsed / num_batches))
@@ -249,6 +325,42 @@ def main(argv=None):
                         'num_batches': num_batches, 'seconds': elapsed, 'synthetic': bool(F.synthetic),
                         'checkpoint': ckpt}, **extra), f)
     return mAP07, mAP12
+
+
+def match_by_area(ops, scores, boxes, glabels, gboxes, gcount, thresholds, ranges, first_label):
+    """ops.match_detections_area over all rows of `ranges`: one launch for up to MAX_AREA_RANGES
+    rows (the all-range slot and seven named ranges); an eighth named range takes a second."""
+    outs = [ops.match_detections_area(scores, boxes, glabels, gboxes, gcount, thresholds, ranges[k:k + MAX_AREA_RANGES],
+                                      first_label=first_label) for k in range(0, len(ranges), MAX_AREA_RANGES)]
+    return outs[0] if len(outs) == 1 else tuple(torch.cat(o) for o in zip(*outs))
+
+
+def area_outputs(F, tfe, per_range, by07, by12):
+    """The *_by_area entries of eval.json from SweepTPFP's per-range tuples and APs (named ranges
+    only), and one printed line per range.  Bit 0 is --matching_threshold."""
+    names = F.area_names
+    out = {'area_ranges': {n: [float(lo), float(hi)] for n, (lo, hi) in zip(names, F.area_ranges_px)},
+           'area_image_size': list(F.area_image_size),
+           'n_gt_by_area': {n: {c: v[0] for c, v in per_range[r][0].items()} for r, n in enumerate(names)},
+           'AP_VOC07_by_area': {n: by07[r][0] for r, n in enumerate(names)},
+           'AP_VOC12_by_area': {n: by12[r][0] for r, n in enumerate(names)},
+           'recall_by_area': {n: {c: float(np.sum(v[2])) / v[0] if v[0] else None for c, v in per_range[r][0].items()}
+                              for r, n in enumerate(names)}}
+    out['mAP_VOC07_by_area'] = {n: tfe.mean_ap(out['AP_VOC07_by_area'][n]) for n in names}
+    out['mAP_VOC12_by_area'] = {n: tfe.mean_ap(out['AP_VOC12_by_area'][n]) for n in names}
+    if F.sweep_thresholds.size:
+        bits = [int(np.nonzero(F.match_thresholds == t)[0][0]) for t in F.sweep_thresholds]
+        for key, by in (('mAP_VOC07_sweep_by_area', by07), ('mAP_VOC12_sweep_by_area', by12)):
+            out[key] = {n: tfe.mean_ap({b: tfe.mean_ap(by[r][b]) for b in bits}) for r, n in enumerate(names)}
+    for r, n in enumerate(names):
+        line = 'area %s [%g, %g) px^2  n_gt %d  AP_VOC07/mAP[%s]  AP_VOC12/mAP[%s]' % (
+            n, F.area_ranges_px[r][0], F.area_ranges_px[r][1], sum(out['n_gt_by_area'][n].values()),
+            out['mAP_VOC07_by_area'][n], out['mAP_VOC12_by_area'][n])
+        if F.sweep_thresholds.size:
+            line += '  sweep mean AP_VOC07/mAP[%s]  AP_VOC12/mAP[%s]' % (out['mAP_VOC07_sweep_by_area'][n],
+                                                                        out['mAP_VOC12_sweep_by_area'][n])
+        print(line)
+    return out
 
 
 if __name__ == '__main__':

@@ -2123,6 +2123,35 @@ def match_detections(scores, boxes, glabels, gboxes, gcount, thresholds, gdiffic
     return tp, fp, n_gt
 
 
+def match_detections_area(scores, boxes, glabels, gboxes, gcount, thresholds, area_ranges, gdifficult=None,
+                          first_label=1):
+    """rod_match_detections_area: match_detections reported for the R object-area ranges of the
+    device fp32 tensor `area_ranges` [R, 2] ((lo, hi) in the boxes' normalised area units, lo
+    inclusive, hi exclusive): ground truth outside a range is ignored, a detection matched to it
+    is neither TP nor FP, an unmatched detection is an FP only of the ranges its own area lies in
+    (semantics in include/rod.h).  Returns (tp_mask, fp_mask) int32 [R, B, C, N] and n_gt int32
+    [R, B, C].  Device tensors in, device tensors out, no sync."""
+    B, C, N = scores.shape
+    G = glabels.shape[1]
+    dev = scores.device
+    if thresholds.device != dev or thresholds.dtype != torch.float32:
+        raise ValueError('match_detections_area: thresholds must be a float32 tensor on %s' % (dev,))
+    if area_ranges.device != dev or area_ranges.dtype != torch.float32:
+        raise ValueError('match_detections_area: area_ranges must be a float32 tensor on %s' % (dev,))
+    if area_ranges.dim() != 2 or area_ranges.shape[1] != 2:
+        raise ValueError('match_detections_area: area_ranges must be [R, 2], got %s' % (tuple(area_ranges.shape),))
+    R = int(area_ranges.shape[0])
+    i32 = lambda t: t.to(torch.int32).contiguous()  # noqa: E731
+    gd = None if gdifficult is None else gdifficult.to(torch.uint8).contiguous()
+    tp = torch.empty((R, B, C, N), dtype=torch.int32, device=dev)
+    fp = torch.empty((R, B, C, N), dtype=torch.int32, device=dev)
+    n_gt = torch.empty((R, B, C), dtype=torch.int32, device=dev)
+    _abi.call("rod_match_detections_area", scores.contiguous(), boxes.float().contiguous(), i32(glabels),
+              gboxes.float().contiguous(), gd, i32(gcount), thresholds.contiguous(), area_ranges.contiguous(), B, C,
+              N, G, int(thresholds.numel()), R, int(first_label), tp, fp, n_gt, stream())
+    return tp, fp, n_gt
+
+
 # ----------------------------------------------------------------------------- VGG-16 ops (F3)
 # slim.conv2d with activation_fn and no normaliser (vgg_arg_scope: relu, nets/backbone/vgg.py:58):
 # the conv's output y is left as an owned Pending with an identity BatchNorm (mean 0, rstd 1,

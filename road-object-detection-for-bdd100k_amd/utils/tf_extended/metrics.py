@@ -1,13 +1,14 @@
 """utils/tf_extended/metrics.py — streaming TP/FP arrays, precision/recall, VOC07/VOC12 AP
 (metrics.py:100-258), host numpy float64 as in the reference.  SweepTPFP (opt-in, not in the
 reference) accumulates the device matcher's per-threshold TP/FP bit masks on the device and
-applies the same host rules once, at the end of the run."""
+applies the same host rules once, at the end of the run; with area_ranges it does so for the
+per-range masks of the area matcher."""
 import numpy as np
 
 from utils.tf_extended.math import cummax
 
-__all__ = ['streaming_tp_fp_arrays', 'StreamingTPFP', 'SweepTPFP', 'precision_recall', 'average_precision_voc07',
-           'average_precision_voc12']
+__all__ = ['streaming_tp_fp_arrays', 'StreamingTPFP', 'SweepTPFP', 'sweep_average_precisions', 'mean_ap',
+           'precision_recall', 'average_precision_voc07', 'average_precision_voc12']
 
 
 class StreamingTPFP(object):
@@ -62,10 +63,16 @@ class SweepTPFP(object):
     value() makes ONE device -> host copy of the filled rows and then, per threshold and class,
     applies StreamingTPFP's rule (rows with tp or fp and score > 1e-4 are kept, in batch order)
     to give the reference's metric tuple for precision_recall / average_precision_voc07 / 12.
-    Everything after the copy is host numpy, as in the reference."""
+    Everything after the copy is host numpy, as in the reference.
+
+    With area_ranges (fp32 [R, 2], the (lo, hi) pairs rod.ops.match_detections_area takes) the
+    accumulator takes that op's outputs instead: the buffer is [capacity_images, C, N + R * (2 * N
+    + 1)] — the N scores once, then per range the N tp masks, the N fp masks and n_gt — and
+    value() / average_precisions() gain a leading per-range level.  A (range, class) without
+    ground truth has no AP: None, which mean_ap skips."""
 
     def __init__(self, thresholds, num_classes, capacity_images, keep_top_k, device, first_label=1,
-                 remove_zero_scores=True):
+                 remove_zero_scores=True, area_ranges=None):
         import torch
         self.thresholds = np.array(thresholds, np.float32).reshape(-1)
         if not 1 <= self.thresholds.size <= 16:
@@ -75,33 +82,48 @@ class SweepTPFP(object):
         self.remove_zero_scores = remove_zero_scores
         self.device = torch.device(device)
         self.thresholds_dev = torch.from_numpy(self.thresholds.copy()).to(self.device)
-        self.buf = torch.zeros((self.capacity, self.C, 3 * self.N + 1), dtype=torch.int32, device=self.device)
+        self.area_ranges = None
+        width = 3 * self.N + 1
+        if area_ranges is not None:
+            self.area_ranges = np.array(area_ranges, np.float32)
+            if self.area_ranges.ndim != 2 or self.area_ranges.shape[1] != 2 or not len(self.area_ranges):
+                raise ValueError('SweepTPFP: area_ranges must be [R, 2] with R >= 1, got shape %s'
+                                 % (self.area_ranges.shape,))
+            self.area_ranges_dev = torch.from_numpy(self.area_ranges.copy()).to(self.device)
+            width = self.N + len(self.area_ranges) * (2 * self.N + 1)
+        self.buf = torch.zeros((self.capacity, self.C, width), dtype=torch.int32, device=self.device)
         self.count = 0
 
     def update(self, scores, tp_mask, fp_mask, n_gt):
-        """scores fp32 [B, C, N], tp_mask / fp_mask int32 [B, C, N], n_gt int32 [B, C]."""
+        """scores fp32 [B, C, N], tp_mask / fp_mask int32 [B, C, N], n_gt int32 [B, C]; with
+        area_ranges tp_mask / fp_mask [R, B, C, N] and n_gt [R, B, C]."""
         import torch
         B, N = scores.shape[0], self.N
-        if tuple(scores.shape) != (B, self.C, N) or tuple(n_gt.shape) != (B, self.C):
+        lead = () if self.area_ranges is None else (len(self.area_ranges),)
+        if tuple(scores.shape) != (B, self.C, N) or tuple(n_gt.shape) != lead + (B, self.C):
             raise ValueError('SweepTPFP.update: expected [B, %d, %d] scores, got %s' % (self.C, N, tuple(scores.shape)))
+        if tuple(tp_mask.shape) != lead + (B, self.C, N) or tuple(fp_mask.shape) != lead + (B, self.C, N):
+            raise ValueError('SweepTPFP.update: expected %s masks, got %s'
+                             % (lead + (B, self.C, N), tuple(tp_mask.shape)))
         if scores.dtype != torch.float32:
             raise ValueError('SweepTPFP.update: scores must be float32')
         if self.count + B > self.capacity:
             raise ValueError('SweepTPFP.update: capacity of %d images exceeded' % self.capacity)
         rows = self.buf[self.count:self.count + B]
         rows[:, :, :N].copy_(scores.contiguous().view(torch.int32))
-        rows[:, :, N:2 * N].copy_(tp_mask)
-        rows[:, :, 2 * N:3 * N].copy_(fp_mask)
-        rows[:, :, 3 * N].copy_(n_gt)
+        if self.area_ranges is None:
+            rows[:, :, N:2 * N].copy_(tp_mask)
+            rows[:, :, 2 * N:3 * N].copy_(fp_mask)
+            rows[:, :, 3 * N].copy_(n_gt)
+        else:
+            for r in range(len(self.area_ranges)):
+                o = N + r * (2 * N + 1)
+                rows[:, :, o:o + N].copy_(tp_mask[r])
+                rows[:, :, o + N:o + 2 * N].copy_(fp_mask[r])
+                rows[:, :, o + 2 * N].copy_(n_gt[r])
         self.count += B
 
-    def value(self):
-        """[{label: (num_gbboxes, num_detections, tp, fp, scores)} for each threshold]: the
-        tuples StreamingTPFP.value() gives after the same batches at that threshold."""
-        N = self.N
-        host = self.buf[:self.count].cpu().numpy()          # the run's only device -> host copy
-        scores = np.ascontiguousarray(host[:, :, :N]).view(np.float32)
-        tpm, fpm, n_gt = host[:, :, N:2 * N], host[:, :, 2 * N:3 * N], host[:, :, 3 * N]
+    def _tuples(self, scores, tpm, fpm, n_gt):
         out = []
         for t in range(self.thresholds.size):
             per = {}
@@ -112,15 +134,47 @@ class SweepTPFP(object):
             out.append(per)
         return out
 
+    def value(self):
+        """[{label: (num_gbboxes, num_detections, tp, fp, scores)} for each threshold]: the
+        tuples StreamingTPFP.value() gives after the same batches at that threshold.  With
+        area_ranges: one such list per range."""
+        N = self.N
+        host = self.buf[:self.count].cpu().numpy()          # the run's only device -> host copy
+        scores = np.ascontiguousarray(host[:, :, :N]).view(np.float32)
+        if self.area_ranges is None:
+            return self._tuples(scores, host[:, :, N:2 * N], host[:, :, 2 * N:3 * N], host[:, :, 3 * N])
+        out = []
+        for r in range(len(self.area_ranges)):
+            o = N + r * (2 * N + 1)
+            out.append(self._tuples(scores, host[:, :, o:o + N], host[:, :, o + N:o + 2 * N], host[:, :, o + 2 * N]))
+        return out
+
     def average_precisions(self, value=None):
-        """([{label: AP_VOC07}], [{label: AP_VOC12}]), one dict per threshold."""
+        """([{label: AP_VOC07}], [{label: AP_VOC12}]), one dict per threshold.  With area_ranges:
+        one such list per range, and None in place of the AP of a class that has no ground
+        truth in the range."""
         value = self.value() if value is None else value
-        ap07, ap12 = [], []
-        for per in value:
-            pr = {c: precision_recall(*v) for c, v in per.items()}
-            ap07.append({c: average_precision_voc07(*v) for c, v in pr.items()})
-            ap12.append({c: average_precision_voc12(*v) for c, v in pr.items()})
-        return ap07, ap12
+        if self.area_ranges is not None:
+            both = [sweep_average_precisions(per_t, True) for per_t in value]
+            return [b[0] for b in both], [b[1] for b in both]
+        return sweep_average_precisions(value)
+
+
+def sweep_average_precisions(per_threshold, none_when_empty=False):
+    """([{label: AP_VOC07}], [{label: AP_VOC12}]) of one SweepTPFP per-threshold list;
+    none_when_empty: None in place of the AP of a class without ground truth."""
+    ap07, ap12 = [], []
+    for per in per_threshold:
+        pr = {c: None if none_when_empty and v[0] == 0 else precision_recall(*v) for c, v in per.items()}
+        ap07.append({c: None if v is None else average_precision_voc07(*v) for c, v in pr.items()})
+        ap12.append({c: None if v is None else average_precision_voc12(*v) for c, v in pr.items()})
+    return ap07, ap12
+
+
+def mean_ap(aps):
+    """Mean of {label: AP or None} over the labels that have one; None if none has."""
+    vals = [v for v in aps.values() if v is not None]
+    return sum(vals) / len(vals) if vals else None
 
 
 def _safe_div(a, b):

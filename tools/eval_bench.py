@@ -7,6 +7,8 @@ synthetic BDD-shaped batches with a detector-like score distribution (rod.data):
             utils/tf_extended/bboxes.py at ONE threshold, StreamingTPFP on the host
   device    --match_on device: the NMS kernel, rod_match_detections, SweepTPFP.update — nothing
             leaves the GPU; measured at T=1 (one threshold) and T=10 (the 0.50:0.05:0.95 sweep)
+  area      --ap_area_ranges coco --ap_iou_sweep coco: the NMS kernel, rod_match_detections_area
+            over the all-range slot and COCO's four ranges (R=5, T=10), SweepTPFP.update per range
 
     python tools/eval_bench.py [--batches 8] [--rounds 7] [--out profiles/evalmatch_bench.json]
 
@@ -16,7 +18,9 @@ device synchronisation before the clock starts and after the last batch only; th
 alternate within a round, after a warm-up round, and the median round is reported with the
 spread, as seconds per batch.  `device_*_final_s` is the one device -> host copy plus the host AP
 arithmetic at the end of a run of `batches` batches (paid once per run, not per batch).
-`match_kernel_us` is rod_match_detections alone, device events around back-to-back launches.
+`match_kernel_us` is rod_match_detections alone, device events around back-to-back launches;
+`area_R5_T10` there is rod_match_detections_area alone, measured the same way in the same run (the
+value to read it against is `T10`).  The default evaluator runs none of the area code.
 No pass condition: the question this answers is whether T=10 on the device costs no more than
 T=1 on the host.
 """
@@ -34,6 +38,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import config  # noqa: E402
+import evaluate  # noqa: E402
 from rod import ops  # noqa: E402
 from rod.data import detector_like_scores, synthetic_batch  # noqa: E402
 from utils import net_tools  # noqa: E402
@@ -88,7 +93,24 @@ def main():
             return acc
         return run
     sweep = np.linspace(0.5, 0.95, 10).astype(np.float32)
-    paths = {'host': host_run, 'device_T1': device_run(sweep[:1]), 'device_T10': device_run(sweep)}
+    # evaluate.py --ap_area_ranges coco at the 720x1280 frame: slot 0 is (-inf, +inf), as there
+    names, px = evaluate.parse_area_ranges('coco')
+    slots = np.concatenate([np.array([[-np.inf, np.inf]], np.float32), evaluate.area_ranges_normalised(px, hw)])
+
+    def area_run():
+        acc = tfe.SweepTPFP(sweep, len(classes), a.batches * B, KW['keep_top_k'], dev, first_label=classes[0],
+                            area_ranges=slots)
+
+        def run():
+            acc.count = 0
+            for probs, boxes, gboxes, glabels, gn in data:
+                s, bx = net_tools.detected_bboxes_packed(probs, boxes, **KW)
+                acc.update(s, *evaluate.match_by_area(ops, s, bx, glabels, gboxes, gn, acc.thresholds_dev,
+                                                      acc.area_ranges_dev, classes[0]))
+            return acc
+        return run
+    paths = {'host': host_run, 'device_T1': device_run(sweep[:1]), 'device_T10': device_run(sweep),
+             'device_area_R5_T10': area_run()}
     times = {k: [] for k in paths}
     final = {k: [] for k in paths if k != 'host'}
     for r in range(a.rounds + 1):            # round 0 is the warm-up
@@ -109,9 +131,13 @@ def main():
     # the two paths give the same AP at 0.5
     state = host_run()
     ap07, ap12 = paths['device_T10']().average_precisions()
+    area_value = paths['device_area_R5_T10']().value()
+    area12 = tfe.sweep_average_precisions(area_value[0])[1]
     for c in classes:
         prec, rec = tfe.precision_recall(*state[c].value())
         assert tfe.average_precision_voc12(prec, rec) == ap12[0][c], c
+        assert area12[0][c] == ap12[0][c], c            # the all-range slot is rod_match_detections' answer
+    n_gt_by_area = {n: int(sum(v[0] for v in area_value[1 + r][0].values())) for r, n in enumerate(names)}
 
     kern = {}
     probs, boxes, gboxes, glabels, gn = data[0]
@@ -127,6 +153,16 @@ def main():
         e1.record()
         e1.synchronize()
         kern[name] = e0.elapsed_time(e1) * 1e3 / a.launches
+    td, rd = torch.from_numpy(sweep).to(dev), torch.from_numpy(slots).to(dev)
+    for _ in range(10):
+        ops.match_detections_area(s, bx, glabels, gboxes, gn, td, rd)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(a.launches):
+        ops.match_detections_area(s, bx, glabels, gboxes, gn, td, rd)
+    e1.record()
+    e1.synchronize()
+    kern['area_R5_T10'] = e0.elapsed_time(e1) * 1e3 / a.launches
 
     med = {k: statistics.median(v) for k, v in times.items()}
     rec = {'device': torch.cuda.get_device_name(0),
@@ -139,7 +175,11 @@ def main():
            'seconds_per_batch': {k: {'median': med[k], 'min': min(v), 'max': max(v)} for k, v in times.items()},
            'device_T1_final_s': statistics.median(final['device_T1']),
            'device_T10_final_s': statistics.median(final['device_T10']),
-           'match_kernel_us': {'T1': kern['T1'], 'T10': kern['T10'],
+           'device_area_R5_T10_final_s': statistics.median(final['device_area_R5_T10']),
+           'area_ranges_px': {n: [lo, 'inf' if np.isinf(hi) else hi] for n, (lo, hi) in zip(names, px.tolist())},
+           'n_gt_by_area': n_gt_by_area,
+           'device_area_over_device_T10': med['device_area_R5_T10'] / med['device_T10'],
+           'match_kernel_us': {'T1': kern['T1'], 'T10': kern['T10'], 'area_R5_T10': kern['area_R5_T10'],
                                'timing': 'device events around %d back-to-back eager launches (launch-bound '
                                          'when the kernel is shorter than a launch)' % a.launches},
            'host_over_device_T10': med['host'] / med['device_T10'],
