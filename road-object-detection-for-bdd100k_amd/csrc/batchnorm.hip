@@ -15,6 +15,7 @@
 #include <mutex>
 
 #include "rod_common.h"
+#include "bnstat_common.h"
 
 namespace rod {
 
@@ -106,11 +107,10 @@ __global__ void __launch_bounds__(256) bn_stats_kernel(const T* __restrict__ x, 
     }
     return;
   }
-  float s1[V], s2[V], k[V];
-#pragma unroll
-  for (int v = 0; v < V; ++v) s1[v] = s2[v] = 0.f;
+  StatAcc<V> st;
+  st.zero();
   if (active) {
-    load_v<T, VEC>(x + r0 * ldx + c, k);
+    load_v<T, VEC>(x + r0 * ldx + c, st.piv);
     long r = r0 + pln;
     for (; r + 3L * lanes < r1; r += 4L * lanes) {
       float a[4][V];
@@ -119,27 +119,19 @@ __global__ void __launch_bounds__(256) bn_stats_kernel(const T* __restrict__ x, 
 #pragma unroll
       for (int u = 0; u < 4; ++u)
 #pragma unroll
-        for (int v = 0; v < V; ++v) {
-          const float d = a[u][v] - k[v];
-          s1[v] += d;
-          s2[v] = fmaf(d, d, s2[v]);
-        }
+        for (int v = 0; v < V; ++v) st.add(v, a[u][v]);
     }
     for (; r < r1; r += lanes) {
       float a[V];
       load_v<T, VEC>(x + r * ldx + c, a);
 #pragma unroll
-      for (int v = 0; v < V; ++v) {
-        const float d = a[v] - k[v];
-        s1[v] += d;
-        s2[v] = fmaf(d, d, s2[v]);
-      }
+      for (int v = 0; v < V; ++v) st.add(v, a[v]);
     }
   }
 #pragma unroll
   for (int v = 0; v < V; ++v) {
-    red[tid * V + v] = s1[v];
-    red[(256 + tid) * V + v] = s2[v];
+    red[tid * V + v] = st.s1[v];
+    red[(256 + tid) * V + v] = st.s2[v];
   }
   __syncthreads();
   const double nb = (double)(r1 - r0);
@@ -153,9 +145,9 @@ __global__ void __launch_bounds__(256) bn_stats_kernel(const T* __restrict__ x, 
       b += (double)red[(256 + l * CVb + cb) * V + v];
     }
     const int ch = cg * V + v;
-    const double kk = (double)to_f32(x[r0 * ldx + ch]);
-    const double m2 = b - a * a / nb;
-    store_stat_part(slab, C, blockIdx.x, ch, (float)nb, (float)(kk + a / nb), (float)(m2 > 0.0 ? m2 : 0.0));
+    float mean, m2;
+    stat_finish_f64(nb, (double)to_f32(x[r0 * ldx + ch]), a, b, mean, m2);
+    store_stat_part(slab, C, blockIdx.x, ch, (float)nb, mean, m2);
   }
 }
 

@@ -11,6 +11,7 @@
 #include "rod_common.h"
 #include "dw_common.h"
 #include "dwfused_common.h"
+#include "bnstat_common.h"
 
 namespace rod {
 
@@ -69,7 +70,9 @@ __global__ void __launch_bounds__(256) dw3x3_fwd_kernel(const T* __restrict__ x,
   const int n = blockIdx.z;
   const int c = cv * V;
   // STATS: shifted sums of this thread's rounded outputs (pivot = its first output), for
-  // its (n, mean, M2) per channel
+  // its (n, mean, M2) per channel.  StatAcc::add and stat_finish_inv written out (bnstat_common.h:
+  // the same operations in the same order): through the helpers the bf16 4-channel form took 132
+  // VGPRs for 128 and lost a wave per SIMD.
   float piv[V], s1[V], s2[V];
 #pragma unroll
   for (int v = 0; v < V; ++v) piv[v] = s1[v] = s2[v] = 0.f;
@@ -280,7 +283,7 @@ __device__ __forceinline__ void dw_lx_body(const T* __restrict__ x, const float*
   // LDS: prefetch ring of D input rows (S=2: column pairs) + the double-buffered exchange
   // slot; the statistics merge reuses the front after the row loop
   constexpr int XS = 2 * 256 * 16;            // double-buffered exchange slot
-  constexpr int SS = STATS ? (256 * (2 * V + 1) + 3 * 512) * 4 : (GRED ? 256 * 2 * V * 4 : 0);
+  constexpr int SS = STATS ? stat_runs_floats(V) * 4 : (GRED ? 256 * 2 * V * 4 : 0);
   __shared__ __attribute__((aligned(16))) char smem[XS > SS ? XS : SS];
   T* xs = (T*)smem;
   const int tid = threadIdx.x;
@@ -311,6 +314,9 @@ __device__ __forceinline__ void dw_lx_body(const T* __restrict__ x, const float*
   const T* xn = x + (long)n * H * W * C + c;
   T* yn = y + (long)n * Ho * Wo * C + c;
 
+  // STATS: StatAcc::add, stat_finish_inv and stat_block_merge_runs (bnstat_common.h) written out —
+  // the same operations in the same order; through the helpers the bf16 statistics forms measured
+  // 1-2.6 % slower (tools/dw_bench.py fwdpro)
   float piv[V], s1[V], s2[V];
 #pragma unroll
   for (int v = 0; v < V; ++v) piv[v] = s1[v] = s2[v] = 0.f;

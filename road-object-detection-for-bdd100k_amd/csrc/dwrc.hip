@@ -23,6 +23,7 @@
 #include "rod_common.h"
 #include "dw_common.h"
 #include "dwfused_common.h"
+#include "bnstat_common.h"
 
 namespace rod {
 
@@ -57,7 +58,7 @@ inline DwRcLds dw_rc_lds(const DwTile& t, int S, int V, int Cin) {
   l.xs = (size_t)2 * l.npt * 16 * RC_XLD * 2;
   l.ys = (size_t)2 * l.npt * 16 * l.ldy * 2;
   l.tabs = (size_t)(2 * Cin + 2 * l.nct * 16) * 4;
-  const size_t stats = (size_t)(256 * (2 * V + 1) + 3 * 512) * 4;   // the epilogue merge (reuses the front)
+  const size_t stats = (size_t)stat_runs_floats(V) * 4;   // the epilogue merge (reuses the front)
   l.total = std::max(l.xs + l.ys + l.tabs, stats);
   return l;
 }
@@ -200,9 +201,8 @@ __global__ void __launch_bounds__(256) dw3x3_fwd_rc_kernel(DwRcArgs a, DwTile tl
   };
 
   // ---- outputs and statistics (dw_lx_body's) --------------------------------------------------
-  float piv[V], s1[V], s2[V];
-#pragma unroll
-  for (int v = 0; v < V; ++v) piv[v] = s1[v] = s2[v] = 0.f;
+  StatAcc<V> st;
+  st.zero();
   const unsigned es = sizeof(T);
   T* yn = a.y + (long)n * Ho * Wo * C + c;
   const rsrc_t rys = rod_rsrc(yn - c, (unsigned)((long)Ho * Wo * C * es));
@@ -216,13 +216,7 @@ __global__ void __launch_bounds__(256) dw3x3_fwd_rc_kernel(DwRcArgs a, DwTile tl
     if constexpr (STATS) {
       if (valid) {
 #pragma unroll
-        for (int v = 0; v < V; ++v) {
-          const float ov = o.get(v);
-          if (first) piv[v] = ov;
-          const float d = ov - piv[v];
-          s1[v] += d;
-          s2[v] = fmaf(d, d, s2[v]);
-        }
+        for (int v = 0; v < V; ++v) st.add(v, o.get(v), first);
       }
     }
     o.bstore(valid ? rys : rnull, vy, (unsigned)(valid ? ho : 0) * rsy);
@@ -339,44 +333,9 @@ __global__ void __launch_bounds__(256) dw3x3_fwd_rc_kernel(DwRcArgs a, DwTile tl
   }
 
   if constexpr (STATS) {
-    // dw_lx_body's merge: per thread (n, mean, M2), runs of 8 columns, then the runs -> part
-    __syncthreads();
-    float* sm = (float*)smem;
-    float* sq = sm + 256 * V;
-    float* sn = sq + 256 * V;
-    const int nr = comp ? ho1 - ho0 : 0;
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-      const float inv = nr > 0 ? 1.f / (float)nr : 0.f;
-      const float dm = s1[v] * inv;
-      sm[tid * V + v] = piv[v] + dm;
-      sq[tid * V + v] = nr > 0 ? fmaxf(s2[v] - s1[v] * dm, 0.f) : 0.f;
-    }
-    sn[tid] = (float)nr;
-    __syncthreads();
-    const int nrun = (P + 7) / 8;
-    float* l1n = sn + 256;
-    float* l1m = l1n + 512;
-    float* l1q = l1m + 512;
-    for (int e = tid; e < Cc * nrun; e += 256) {
-      const int ch = e % Cc, run = e / Cc;
-      const int cve = ch / V, v = ch - cve * V;
-      float pn = 0.f, pm = 0.f, pq = 0.f;
-      for (int pp = run * 8; pp < run * 8 + 8 && pp < P; ++pp) {
-        const int t2 = pp * CVb + cve;
-        chan_merge(pn, pm, pq, sn[t2], sm[t2 * V + v], sq[t2 * V + v]);
-      }
-      l1n[e] = pn;
-      l1m[e] = pm;
-      l1q[e] = pq;
-    }
-    __syncthreads();
+    // dw_lx_body's merge
     const long part = ((long)n * tl.strips + strip) * tl.coltiles + ct;
-    for (int ch = tid; ch < Cc; ch += 256) {
-      float pn = 0.f, pm = 0.f, pq = 0.f;
-      for (int run = 0; run < nrun; ++run) chan_merge(pn, pm, pq, l1n[run * Cc + ch], l1m[run * Cc + ch], l1q[run * Cc + ch]);
-      store_stat_part(a.parts, C, part, cg * Cc + ch, pn, pm, pq);
-    }
+    stat_block_merge_runs<V>((float*)smem, tid, comp ? ho1 - ho0 : 0, st, CVb, P, a.parts, C, part, cg * Cc);
   }
 }
 

@@ -13,6 +13,7 @@
 // The f32 16x16x4 form is issued 8 times per 32-deep k-step with lane l contributing
 // k = 8(l>>4)+j in issue j, so both dtypes read the same 8-element k-runs from LDS.
 #include "rod_common.h"
+#include "bnstat_common.h"
 
 namespace rod {
 
@@ -334,9 +335,7 @@ __global__ void __launch_bounds__(256) conv_fwd_kernel(const T* __restrict__ X, 
   constexpr int LDC = BN + EV;
   constexpr int MAIN_BYTES = (BM + BN) * LD * sizeof(T);
   constexpr int EPI_BYTES = VY ? 64 * LDC * sizeof(T) : 0;
-  constexpr int ST_BYTES = 0;
-  constexpr int SM1 = MAIN_BYTES > EPI_BYTES ? MAIN_BYTES : EPI_BYTES;
-  constexpr int SMEM = SM1 > ST_BYTES ? SM1 : ST_BYTES;
+  constexpr int SMEM = MAIN_BYTES > EPI_BYTES ? MAIN_BYTES : EPI_BYTES;
   __shared__ __attribute__((aligned(16))) char smem[SMEM];
   T* As = (T*)smem;  // A tile, B tile after it
 
@@ -521,11 +520,6 @@ __global__ void __launch_bounds__(256) conv_fwd_kernel(const T* __restrict__ X, 
     }
     T* Cs = (T*)smem;
     constexpr int WROWS = BM / WM;  // rows per wave
-    // BatchNorm partial statistics of this 128-row tile (STATS) and the gred sums (GRED) walk
-    // the staged (already rounded) rows of each half: a thread owns one EV-wide column chunk
-    // and the rows GRPP apart, reading 16-byte LDS chunks.  STATS: one pass of sums shifted by
-    // a pivot per column common to the whole tile (the mean of its first <= 8 rows, so the
-    // shifted sums do not cancel), combined over the row groups by plain addition.
     // GRED: BatchNorm-backward sums of this tile's rounded outputs (dz, staged in Cs) against
     // y_in; a thread owns one EV-wide column chunk and walks rows GRPP apart, so each pass of
     // the block reads whole 16-byte row segments of y_in (coalesced, all loads independent)
@@ -534,13 +528,12 @@ __global__ void __launch_bounds__(256) conv_fwd_kernel(const T* __restrict__ X, 
     const int gcc = (tid % GCPR) * EV, grg = tid / GCPR;
     const int gcol = n0 + gcc;
     const bool gact = GRED && grg < GRPP && gcol < Cout;
-    // STATS from the accumulators, before staging: a column of a 16x16 MFMA tile lives in the
-    // four lanes l, l^16, l^32, l^48 (rows 4(l>>4)+r).  Per wave and column: pivot = mean of the
-    // wave strip's first (up to) 8 valid rows, then sums of (v - pivot), (v - pivot)^2 over the
-    // strip's valid rows (v = the output rounded to T), combined across the four lane groups by
-    // shuffles -> (n, mean, M2) per wave; the WM waves are Chan-merged in order at the end.
-    // per-wave (count, mean, M2) of each column: [WM][3][BN] floats in their own LDS (written
-    // here, read after the staging loop, whose barriers order the two)
+    // STATS: BatchNorm partial statistics of this 128-row tile, taken from the accumulators before
+    // staging (bnstat_common.h, the MFMA-column form).  Per wave and column: pivot = mean of the
+    // wave strip's first (up to) 8 valid rows, then the shifted sums over the strip's valid rows
+    // of the output rounded to T, combined across the four lane groups -> (n, mean, M2) per wave
+    // in wst [WM][3][BN] (its own LDS: written here, read after the staging loop, whose barriers
+    // order the two), where the WM strips are merged in order at the end.
     __shared__ float wst[(VY && STATS) ? WM * 3 * BN : 1];
     if constexpr (STATS) {
       // round once, in place: the statistics and the staging below use the stored values
@@ -554,61 +547,23 @@ __global__ void __launch_bounds__(256) conv_fwd_kernel(const T* __restrict__ X, 
       // rows of this wave's strip still inside M (all of them except in the last tile)
       const long left_l = M - (m0 + wm * WROWS);
       const int left = left_l > WROWS ? WROWS : (left_l < 0 ? 0 : (int)left_l);
+      const bool full = left == WROWS;  // full strip: no row checks
 #pragma unroll
       for (int b = 0; b < NT; ++b) {
-        float p = 0.f, pc = 0.f;
-        if (lg < 2) {
+        StatAcc<1> st;
+        st.zero();
+        st.piv[0] = mfma_col_pivot(acc[0][b], lane, left);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            if (lg * 4 + r < left) {
-              p += acc[0][b][r];
-              pc += 1.f;
-            }
-          }
-        }
-        p += __shfl_xor(p, 16, 64);
-        pc += __shfl_xor(pc, 16, 64);
-        p = __shfl(p, lane & 15, 64);
-        pc = __shfl(pc, lane & 15, 64);
-        // full strips: pc = 8 and the division is an exact scaling
-        const float piv = left >= 8 ? p * 0.125f : (pc > 0.f ? p / pc : 0.f);
-        float s1 = 0.f, s2 = 0.f, n = 0.f;
-        if (left == WROWS) {  // full strip: no row checks
+        for (int a = 0; a < MT; ++a)
 #pragma unroll
-          for (int a = 0; a < MT; ++a)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const float d = acc[a][b][r] - piv;
-              s1 += d;
-              s2 = fmaf(d, d, s2);
-            }
-          n = (float)(MT * 4);
-        } else {
-#pragma unroll
-          for (int a = 0; a < MT; ++a)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              if (a * 16 + lg * 4 + r < left) {
-                const float d = acc[a][b][r] - piv;
-                s1 += d;
-                s2 = fmaf(d, d, s2);
-                n += 1.f;
-              }
-            }
-        }
-        s1 += __shfl_xor(s1, 16, 64);
-        s2 += __shfl_xor(s2, 16, 64);
-        n += __shfl_xor(n, 16, 64);
-        s1 += __shfl_xor(s1, 32, 64);
-        s2 += __shfl_xor(s2, 32, 64);
-        n += __shfl_xor(n, 32, 64);
+          for (int r = 0; r < 4; ++r)
+            if (full || a * 16 + lg * 4 + r < left) st.add(0, acc[a][b][r]);
+        mfma_col_reduce(st.s1[0], st.s2[0]);
         if (lane < 16) {
-          static_assert((WROWS & (WROWS - 1)) == 0, "wave strip must be a power of two");
-          const float dm = left == WROWS ? s1 * (1.0f / WROWS) : (n > 0.f ? s1 / n : 0.f);
           const int cl = wn * (BN / WN) + b * 16 + lane;
-          wst[(wm * 3 + 0) * BN + cl] = n;
-          wst[(wm * 3 + 1) * BN + cl] = piv + dm;
-          wst[(wm * 3 + 2) * BN + cl] = fmaxf(s2 - s1 * dm, 0.f);
+          wst[(wm * 3 + 0) * BN + cl] = (float)left;
+          stat_finish_tile<WROWS>(full, (float)left, st.piv[0], st.s1[0], st.s2[0], wst[(wm * 3 + 1) * BN + cl],
+                                  wst[(wm * 3 + 2) * BN + cl]);
         }
       }
     }
@@ -727,16 +682,8 @@ __global__ void __launch_bounds__(256) conv_fwd_kernel(const T* __restrict__ X, 
       const float* st = wst;
       if (tid < BN && n0 + tid < Cout) {
         float n = st[tid], mu = st[BN + tid], m2 = st[2 * BN + tid];
-        for (int w = 1; w < WM; ++w) {  // Chan merge in wave order
-          const float nb = st[(w * 3) * BN + tid];
-          if (nb <= 0.f) continue;
-          const float mb = st[(w * 3 + 1) * BN + tid], m2b = st[(w * 3 + 2) * BN + tid];
-          const float nn = n + nb;
-          const float d = mb - mu;
-          mu = mu + d * (nb / nn);
-          m2 = m2 + m2b + d * d * (n * nb / nn);
-          n = nn;
-        }
+        for (int w = 1; w < WM; ++w)  // the wave strips, in order
+          chan_merge_strip(n, mu, m2, st[(w * 3) * BN + tid], st[(w * 3 + 1) * BN + tid], st[(w * 3 + 2) * BN + tid]);
         store_stat_part(part, Cout, mt, n0 + tid, n, mu, m2);
       }
     }
@@ -939,9 +886,8 @@ __global__ void __launch_bounds__(256, (PRO && KT >= 5) ? 4 : (MODE == 3 ? 5 : 1
     const long row0 = t * 128;
     const int left = M - row0 < 128 ? (int)(M - row0) : 128;  // valid rows of this tile
     const bool full = left == 128;
-    float piv[NT], s1[NT], s2[NT];
-#pragma unroll
-    for (int b = 0; b < NT; ++b) piv[b] = s1[b] = s2[b] = 0.f;
+    StatAcc<NT> st;
+    st.zero();
 #pragma unroll 1
     for (int s = 0; s < SUB; ++s) {
       const long rs = row0 + s * 16;
@@ -980,7 +926,8 @@ __global__ void __launch_bounds__(256, (PRO && KT >= 5) ? 4 : (MODE == 3 ? 5 : 1
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = (float)(bf16_t)acc[b][r];
         if constexpr (STATS) {
-          if (s == 0) {  // pivot: mean of the tile's first (up to) 8 valid rows, this column
+          if (s == 0) {  // pivot: mean of the tile's first (up to) 8 valid rows, this column (mfma_col_pivot's
+                         // values, kept inline here: as a call it cost registers)
             float p = 0.f;
             if (lg < 2) {
 #pragma unroll
@@ -990,16 +937,11 @@ __global__ void __launch_bounds__(256, (PRO && KT >= 5) ? 4 : (MODE == 3 ? 5 : 1
             p += __shfl_xor(p, 16, 64);
             p = __shfl(p, fr, 64);
             const int pc = left < 8 ? left : 8;
-            piv[b] = full ? p * 0.125f : p / (float)pc;
+            st.piv[b] = full ? p * 0.125f : p / (float)pc;
           }
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            if (full || s * 16 + lg * 4 + r < left) {
-              const float d = v[r] - piv[b];
-              s1[b] += d;
-              s2[b] = fmaf(d, d, s2[b]);
-            }
-          }
+          for (int r = 0; r < 4; ++r)
+            if (full || s * 16 + lg * 4 + r < left) st.add(b, v[r]);
         }
         if constexpr (!NOSTORE) {
 #pragma unroll
@@ -1043,14 +985,12 @@ __global__ void __launch_bounds__(256, (PRO && KT >= 5) ? 4 : (MODE == 3 ? 5 : 1
       const float n = (float)left;
 #pragma unroll
       for (int b = 0; b < NT; ++b) {
-        float a = s1[b], q = s2[b];
-        a += __shfl_xor(a, 16, 64);
-        q += __shfl_xor(q, 16, 64);
-        a += __shfl_xor(a, 32, 64);
-        q += __shfl_xor(q, 32, 64);
+        float a = st.s1[b], q = st.s2[b];
+        mfma_col_reduce(a, q);
         if (lane < 16 && n0 + b * 16 + lane < Cout) {
-          const float dm = full ? a * (1.0f / 128.0f) : a / n;
-          store_stat_part(part, Cout, t, n0 + b * 16 + lane, n, piv[b] + dm, fmaxf(q - a * dm, 0.f));
+          float mean, m2;
+          stat_finish_tile<128>(full, n, st.piv[b], a, q, mean, m2);
+          store_stat_part(part, Cout, t, n0 + b * 16 + lane, n, mean, m2);
         }
       }
     }
@@ -1449,25 +1389,21 @@ __global__ void __launch_bounds__(256) stem_fwd_mfma_kernel(const bf16_t* __rest
     }
     if constexpr (STATS) {
       const int c = tid >> 3, sub = tid & 7;
-      const float k = (float)Ys[c];  // pivot: pixel 0 of the tile
-      float s1 = 0.f, s2 = 0.f;
+      StatAcc<1> st;
+      st.zero();
+      st.piv[0] = (float)Ys[c];  // pivot: pixel 0 of the tile
 #pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const float d = (float)Ys[(sub * 16 + j) * SW_LD + c] - k;
-        s1 += d;
-        s2 = fmaf(d, d, s2);
-      }
+      for (int j = 0; j < 16; ++j) st.add(0, (float)Ys[(sub * 16 + j) * SW_LD + c]);
 #pragma unroll
       for (int o = 1; o < 8; o <<= 1) {
-        s1 += __shfl_xor(s1, o, 64);
-        s2 += __shfl_xor(s2, o, 64);
+        st.s1[0] += __shfl_xor(st.s1[0], o, 64);
+        st.s2[0] += __shfl_xor(st.s2[0], o, 64);
       }
       if (sub == 0) {
         const long tile = (((long)n * H + y) * W + x0) / SW_TW;
-        const double nb = (double)SW_TW;
-        const double m2 = (double)s2 - (double)s1 * (double)s1 / nb;
-        store_stat_part(stats, 32, tile, c, (float)nb, (float)((double)k + (double)s1 / nb),
-                        (float)(m2 > 0.0 ? m2 : 0.0));
+        float mean, m2;
+        stat_finish_f64((double)SW_TW, (double)st.piv[0], (double)st.s1[0], (double)st.s2[0], mean, m2);
+        store_stat_part(stats, 32, tile, c, (float)SW_TW, mean, m2);
       }
     }
     if (y + 1 < yz) gather(y + 1);   // rows y .. y+2 are in the ring (barrier above)
