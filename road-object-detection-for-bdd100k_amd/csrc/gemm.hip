@@ -14,6 +14,7 @@
 // k = 8(l>>4)+j in issue j, so both dtypes read the same 8-element k-runs from LDS.
 #include "rod_common.h"
 #include "bnstat_common.h"
+#include "pwbwd_common.h"
 
 namespace rod {
 
@@ -1418,13 +1419,6 @@ __global__ void __launch_bounds__(256) stem_fwd_mfma_kernel(const bf16_t* __rest
 constexpr int WG_T = 64;            // co / k tile
 constexpr int WG_LD = WG_T + 4;     // LDS row (elements): 136 B bf16 / 272 B f32
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ bf16x4 tr_read(const bf16_t* p) {
-  s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-  return __builtin_bit_cast(bf16x4, r);
-}
-
 // RPT row chunks per thread per step (bf16: 2, so a block keeps two 32-row steps of loads in
 // flight per barrier pair; the kernel is load-latency bound at <= 8 resident blocks per CU)
 template <typename T, int KS, bool VA, bool VD, int CIN = 0, bool PRO = false>
@@ -1557,14 +1551,14 @@ __global__ void __launch_bounds__(256) conv_wgrad_kernel(const T* __restrict__ X
 #pragma unroll
       for (int a = 0; a < 2; ++a) {
         const int cb = wm * 32 + a * 16;
-        const bf16x4 lo = tr_read((const bf16_t*)Ds + (u * BK + 8 * g + q) * WG_LD + cb + 4 * p);
-        const bf16x4 hi = tr_read((const bf16_t*)Ds + (u * BK + 8 * g + 4 + q) * WG_LD + cb + 4 * p);
+        const bf16x4 lo = lds_tr_read((const bf16_t*)Ds + (u * BK + 8 * g + q) * WG_LD + cb + 4 * p);
+        const bf16x4 hi = lds_tr_read((const bf16_t*)Ds + (u * BK + 8 * g + 4 + q) * WG_LD + cb + 4 * p);
         bf16x8 fa = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
           const int kb = wn * 32 + b * 16;
-          const bf16x4 l2 = tr_read((const bf16_t*)Xs + (u * BK + 8 * g + q) * WG_LD + kb + 4 * p);
-          const bf16x4 h2 = tr_read((const bf16_t*)Xs + (u * BK + 8 * g + 4 + q) * WG_LD + kb + 4 * p);
+          const bf16x4 l2 = lds_tr_read((const bf16_t*)Xs + (u * BK + 8 * g + q) * WG_LD + kb + 4 * p);
+          const bf16x4 h2 = lds_tr_read((const bf16_t*)Xs + (u * BK + 8 * g + 4 + q) * WG_LD + kb + 4 * p);
           bf16x8 fb = {l2[0], l2[1], l2[2], l2[3], h2[0], h2[1], h2[2], h2[3]};
           acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb, acc[a][b], 0, 0, 0);
         }
@@ -1656,30 +1650,13 @@ __global__ void __launch_bounds__(256) stem_wgrad_kernel(const bf16_t* __restric
   const int xx = x0 + px;
   const bool inx = xx < W, inx2 = xx + 64 < W;
   const int pg = tid & 127, hg = tid >> 7;  // gather: pixel, wave-uniform tap half
-  float sc[BNB ? 8 : 1], sh[BNB ? 8 : 1], ca[BNB ? 8 : 1], k1[BNB ? 8 : 1], k0[BNB ? 8 : 1];
+  PbBnD<BNB ? 8 : 1> bd;   // the 1x1 backwards' dy (pwbwd_common.h)
   float ghi = 0.f, glo = 0.f;
   if constexpr (BNB) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int c = ck * 8 + e;
-      bn_affine(bb.mean, bb.rstd, bb.gamma, bb.beta, c, sc[e], sh[e]);
-      ca[e] = bb.coef[c];
-      bn_bwd_k_fold(ca[e], bb.mean[c], bb.rstd[c], bb.coef[32 + c], bb.coef[64 + c], k1[e], k0[e]);
-    }
-    ghi = bb.act == ROD_ACT_RELU6 ? 6.f : INFINITY;
-    glo = bb.act == ROD_ACT_LEAKY ? 0.2f : bb.act == ROD_ACT_NONE ? 1.f : 0.f;
+    bd.init(bb.mean, bb.rstd, bb.gamma, bb.beta, bb.coef, 32, ck * 8);
+    ghi = pb_gate_hi(bb.act), glo = pb_gate_lo(bb.act);
   }
-  auto apply = [&](const bf16x8& dzv, const bf16x8& yv) {
-    bf16x8 o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float yj = (float)yv[e];
-      const float z = fmaf(yj, sc[e], sh[e]);
-      const float gj = (float)dzv[e] * (z > 0.f ? (z < ghi ? 1.f : 0.f) : glo);
-      o[e] = (bf16_t)bn_bwd_apply1<bf16_t>(ca[e], gj, k1[e], k0[e], 0.f, yj);
-    }
-    return o;
-  };
+  auto apply = [&](const bf16x8& dzv, const bf16x8& yv) { return bd.dy(PbGate{ghi, glo}, dzv, yv); };
 
   bf16x8 d0, d1, y0, y1;
   unsigned short tv[16];
@@ -1744,13 +1721,13 @@ __global__ void __launch_bounds__(256) stem_wgrad_kernel(const bf16_t* __restric
     const int m0 = wave * 32;
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
-      const bf16x4 lo = tr_read(Ds + (m0 + 8 * g + q) * SW_LD + a * 16 + 4 * p);
-      const bf16x4 hi = tr_read(Ds + (m0 + 8 * g + 4 + q) * SW_LD + a * 16 + 4 * p);
+      const bf16x4 lo = lds_tr_read(Ds + (m0 + 8 * g + q) * SW_LD + a * 16 + 4 * p);
+      const bf16x4 hi = lds_tr_read(Ds + (m0 + 8 * g + 4 + q) * SW_LD + a * 16 + 4 * p);
       bf16x8 fa = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
-        const bf16x4 l2 = tr_read(Xs + (m0 + 8 * g + q) * SW_LD + b * 16 + 4 * p);
-        const bf16x4 h2 = tr_read(Xs + (m0 + 8 * g + 4 + q) * SW_LD + b * 16 + 4 * p);
+        const bf16x4 l2 = lds_tr_read(Xs + (m0 + 8 * g + q) * SW_LD + b * 16 + 4 * p);
+        const bf16x4 h2 = lds_tr_read(Xs + (m0 + 8 * g + 4 + q) * SW_LD + b * 16 + 4 * p);
         bf16x8 fb = {l2[0], l2[1], l2[2], l2[3], h2[0], h2[1], h2[2], h2[3]};
         acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb, acc[a][b], 0, 0, 0);
       }

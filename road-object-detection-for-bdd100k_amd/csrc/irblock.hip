@@ -57,11 +57,6 @@ struct IrArgs {
   int H, W, Cin, inner, Cout, Ho, Wo, pt, pl, residual;
 };
 
-typedef short ir_s16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ bf16x4 ir_tr_read(const bf16_t* p) {
-  ir_s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) ir_s16x4*)p);
-  return __builtin_bit_cast(bf16x4, r);
-}
 typedef __bf16 ir_bf16x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ float relu6_bf16(float v, float sc, float sh) {
@@ -472,7 +467,7 @@ __global__ void __launch_bounds__(256) ir_block_fwd_kernel(IrArgs a, int ntiles)
       for (int i = 0; i < MTP; ++i) {
         const int mt = wave + 4 * i;
         const bf16_t* pd = Dt + (8 * g + q4) * LDD + mt * 16 + 4 * p4;
-        const bf16x4 lo = ir_tr_read(pd), hi = ir_tr_read(pd + 4 * LDD);
+        const bf16x4 lo = lds_tr_read(pd), hi = lds_tr_read(pd + 4 * LDD);
         const bf16x8 fa = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {

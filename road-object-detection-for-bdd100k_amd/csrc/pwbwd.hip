@@ -23,7 +23,13 @@
 // the 7 coefficient fields are read four channels at a time.  The expand shapes went from
 // 1-2 to 3 waves per SIMD: tools/pwbwd_bench.py 4715 -> 3326 us over its eight shapes,
 // outputs bit-identical.
+//
+// The arithmetic the three kernels of this file share — the gate and dy (pb_dy1), the lane
+// constants, the input prologue, the MFMA tiles, the wave-ordered tails and the 32-row tile
+// bookkeeping — is stated once in pwbwd_common.h; this file keeps what differs: which rows a
+// thread owns, what is in flight when, and the launch plans.
 #include "rod_common.h"
+#include "pwbwd_common.h"
 
 namespace rod {
 
@@ -47,12 +53,6 @@ struct PwBwdArgs {
   const bf16_t* wt0 = nullptr;   // RC (ABI 23): the forward weights [Cout][Cin]; y is recomputed, never read
 };
 
-typedef short pb_s16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ bf16x4 pb_tr_read(const bf16_t* p) {
-  pb_s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) pb_s16x4*)p);
-  return __builtin_bit_cast(bf16x4, r);
-}
-
 template <int NX, int WT>
 __global__ void __launch_bounds__(256) pw_bwd_kernel(PwBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -71,21 +71,14 @@ __global__ void __launch_bounds__(256) pw_bwd_kernel(PwBwdArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: tile indices in SGPRs
   const bool prox = a.xmean != nullptr;
   const bool has_bias = a.partb != nullptr;
-  // act_grad(z, act) as one select chain: z > 0 ? (z < hi ? 1 : 0) : lo — the same {0, 0.2, 1}
-  // factors (NaN -> lo, as the compare-based forms give) without a per-element switch
-  const float ghi = a.act == ROD_ACT_RELU6 ? 6.f : INFINITY;
-  const float glo = a.act == ROD_ACT_LEAKY ? 0.2f : a.act == ROD_ACT_NONE ? 1.f : 0.f;
+  const float ghi = pb_gate_hi(a.act), glo = pb_gate_lo(a.act);
 
-  for (int c = tid; c < Cout; c += 256) {
-    float sc, sh;
-    bn_affine(a.mean, a.rstd, a.gamma, a.beta, c, sc, sh);
+  for (int c = tid; c < Cout; c += 256) {   // fields 2..6: sc, sh, a, k1, k0 (0, 1, 7: mean, rstd, 0)
     float* t = ctab + c;
     t[0] = a.mean[c];
     t[Cout] = a.rstd[c];
-    t[2 * Cout] = sc;
-    t[3 * Cout] = sh;
-    t[4 * Cout] = a.coef[c];
-    bn_bwd_k_fold(a.coef[c], a.mean[c], a.rstd[c], a.coef[Cout + c], a.coef[2 * Cout + c], t[5 * Cout], t[6 * Cout]);
+    pb_bn_d1(a.mean, a.rstd, a.gamma, a.beta, a.coef, Cout, c, t[2 * Cout], t[3 * Cout], t[4 * Cout], t[5 * Cout],
+             t[6 * Cout]);
     t[7 * Cout] = 0.f;
   }
   if (prox) {
@@ -96,17 +89,11 @@ __global__ void __launch_bounds__(256) pw_bwd_kernel(PwBwdArgs a) {
       xtab[Cin + c] = sh;
     }
   }
-  // zero padding: dy columns >= Cout, a columns >= Cin, the whole W image
-  for (int i = tid; i < PB_BM * LDD; i += 256) Ds[i] = (bf16_t)0.f;
-  for (int i = tid; i < PB_BM * LDX; i += 256) Xs[i] = (bf16_t)0.f;
-  for (int i = tid; i < a.nxt * 16 * LDD; i += 256) Ws[i] = (bf16_t)0.f;
+  // zero padding: dy columns >= Cout, a columns >= Cin, the whole W image (Ds | Xs | Ws are
+  // contiguous, every row a multiple of 16 bytes)
+  pb_lds_zero(Ds, (PB_BM * LDD + PB_BM * LDX + a.nxt * 16 * LDD) / 8, tid);
   __syncthreads();
-  if (a.dx) {
-    for (int i = tid; i < Cin * CCH; i += 256) {
-      const int ci = i / CCH, cc = i - ci * CCH;
-      *(bf16x8*)(Ws + ci * LDD + cc * 8) = *(const bf16x8*)(a.wt1 + (long)ci * Cout + cc * 8);
-    }
-  }
+  if (a.dx) pb_load_wt1(Ws, LDD, a.wt1, Cin, Cout, tid);
 
   const long mb = (long)blockIdx.x * a.chunk;
   const long me = mb + a.chunk < a.M ? mb + a.chunk : a.M;
@@ -168,10 +155,7 @@ __global__ void __launch_bounds__(256) pw_bwd_kernel(PwBwdArgs a) {
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) {
               const int j = 4 * h + jj;
-              const float yj = (float)yv[u][j];
-              const float z = fmaf(yj, f[2][jj], f[3][jj]);
-              const float gj = (float)dv[u][j] * (z > 0.f ? (z < ghi ? 1.f : 0.f) : glo);
-              o[j] = (bf16_t)bn_bwd_apply1<bf16_t>(f[4][jj], gj, f[5][jj], f[6][jj], 0.f, yj);   // fields 5, 6: k1, k0
+              o[j] = (bf16_t)pb_dy1(PbGate{ghi, glo}, f[2][jj], f[3][jj], f[4][jj], f[5][jj], f[6][jj], dv[u][j], yv[u][j]);
             }
           }
         } else {
@@ -189,13 +173,10 @@ __global__ void __launch_bounds__(256) pw_bwd_kernel(PwBwdArgs a) {
       bf16x8 v = xr[k];
       if (m0 + r < me) {
         if (prox) {
-          const f32x4 s0 = *(const f32x4*)(xtab + cc * 8), s1 = *(const f32x4*)(xtab + cc * 8 + 4);
-          const f32x4 h0 = *(const f32x4*)(xtab + Cin + cc * 8), h1 = *(const f32x4*)(xtab + Cin + cc * 8 + 4);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            v[j] = (bf16_t)act_fwd(fmaf((float)v[j], s0[j], h0[j]), a.xact);
-            v[4 + j] = (bf16_t)act_fwd(fmaf((float)v[4 + j], s1[j], h1[j]), a.xact);
-          }
+          float xsc[8], xsh[8];
+          pb_ld8(xtab + cc * 8, xsc);
+          pb_ld8(xtab + Cin + cc * 8, xsh);
+          v = pb_xpro(v, xsc, xsh, a.xact, true);
         }
       } else {
 #pragma unroll
@@ -212,18 +193,12 @@ __global__ void __launch_bounds__(256) pw_bwd_kernel(PwBwdArgs a) {
       if (t >= ntile) continue;
       const int ct = t / a.nci, it = t - ct * a.nci;
 #pragma unroll
-      for (int ks = 0; ks < PB_BM / 32; ++ks) {
-        const bf16_t* pd = Ds + (ks * 32 + 8 * g + q) * LDD + ct * 16 + 4 * p;
-        const bf16_t* px = Xs + (ks * 32 + 8 * g + q) * LDX + it * 16 + 4 * p;
-        const bf16x4 lo = pb_tr_read(pd), hi = pb_tr_read(pd + 4 * LDD);
-        const bf16x4 l2 = pb_tr_read(px), h2 = pb_tr_read(px + 4 * LDX);
-        const bf16x8 fa = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        const bf16x8 fb = {l2[0], l2[1], l2[2], l2[3], h2[0], h2[1], h2[2], h2[3]};
-        accw[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb, accw[i], 0, 0, 0);
-      }
+      for (int ks = 0; ks < PB_BM / 32; ++ks)
+        pb_dw_tile(Ds + ks * 32 * LDD, LDD, Xs + ks * 32 * LDX, LDX, ct, it, tid & 63, accw[i]);
     }
     if (!a.dx) continue;
     // ---- 2b. dx = dy . W for this wave's 16 rows -------------------------------------------
+    // (pb_dx_half's loop with the run-time k depth and tile count of this kernel's plan)
     f32x4 accx[NX];
 #pragma unroll
     for (int j = 0; j < NX; ++j) accx[j] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -293,17 +268,6 @@ __global__ void __launch_bounds__(256) pw_bwd_kernel(PwBwdArgs a) {
 // dx is the block kernel's bit for bit (same dy, same MFMA k order); dW sums its rows in another
 // grouping (fp32, within the float64 bounds of tests/test_gpu_pwbwd.py).
 // =====================================================================================
-typedef float pb_f2 __attribute__((ext_vector_type(2)));
-typedef __bf16 pb_b2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ pb_f2 pb_unpack(unsigned u) {   // bf16 pair (low, high) -> fp32 pair
-  return pb_f2{__builtin_bit_cast(float, u << 16), __builtin_bit_cast(float, u & 0xffff0000u)};
-}
-__device__ __forceinline__ unsigned pb_round(pb_f2 v) {    // one v_cvt_pk_bf16_f32 (RNE per element)
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, pb_b2));
-}
-// ReLU6 gradient gate (0 < z < 6; NaN -> closed) as one unsigned compare on the bits
-__device__ __forceinline__ bool pb_relu6_open(float z) { return __builtin_bit_cast(unsigned, z) - 1u < 0x40BFFFFFu; }
-
 template <int CIN, int COUT>
 struct PbsGeo {
   // CW channels per lane chunk: 4 (8-byte loads) where the chunks tile 64 lanes into whole rows
@@ -368,19 +332,9 @@ __global__ void __launch_bounds__(256, CIN == 16 ? 3 : 1) pw_bwd_stream_kernel(P
   bf16_t* Cx = Xs + 32 * LDX;                                   // [16][LDC]  dx staging
   bf16_t* Wf = Ws + G::WS + G::XT + 4 * G::WREG;                // RC: [COUT][LDW] forward weights
   // zero everything once (dy columns >= COUT, x columns >= CIN stay 0), then the weights
-  for (int i = tid; i < (G::WS + G::XT + 4 * G::WREG + (RC ? G::WF : 0)) / 8; i += 256) {
-    bf16x8 z;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) z[j] = (bf16_t)0.f;
-    ((bf16x8*)smem)[i] = z;
-  }
+  pb_lds_zero(smem, (G::WS + G::XT + 4 * G::WREG + (RC ? G::WF : 0)) / 8, tid);
   __syncthreads();
-  if constexpr (DX) {
-    for (int i = tid; i < CIN * (COUT / 8); i += 256) {
-      const int ci = i / (COUT / 8), c8 = i - ci * (COUT / 8);
-      *(bf16x8*)(Ws + ci * LDD + c8 * 8) = *(const bf16x8*)(a.wt1 + (long)ci * COUT + c8 * 8);
-    }
-  }
+  if constexpr (DX) pb_load_wt1(Ws, LDD, a.wt1, CIN, COUT, tid);
   if constexpr (PRO) {
     for (int c = tid; c < CIN; c += 256) {
       bn_affine(a.xmean, a.xrstd, a.xgamma, a.xbeta, c, xtab[c], xtab[CIN + c]);
@@ -399,31 +353,17 @@ __global__ void __launch_bounds__(256, CIN == 16 ? 3 : 1) pw_bwd_stream_kernel(P
   float xsg[XG ? 8 : 1] = {}, xsgx[XG ? 8 : 1] = {};   // XG: sums of g and g*(x - mean), this lane's chunk
   const int rg = lane / CCH, cc = lane - (lane / CCH) * CCH;
   const bool dact = rg < RG;
-  const int c0 = dact ? cc * CW : 0;
-  float sc[CW], sh[CW], ca[CW], k1[CW], k0[CW];
-#pragma unroll
-  for (int e = 0; e < CW; ++e) {
-    const int c = c0 + e;
-    bn_affine(a.mean, a.rstd, a.gamma, a.beta, c, sc[e], sh[e]);
-    ca[e] = a.coef[c];
-    bn_bwd_k_fold(ca[e], a.mean[c], a.rstd[c], a.coef[COUT + c], a.coef[2 * COUT + c], k1[e], k0[e]);
-  }
-  const float ghi = a.act == ROD_ACT_RELU6 ? 6.f : INFINITY;
-  const float glo = a.act == ROD_ACT_LEAKY ? 0.2f : a.act == ROD_ACT_NONE ? 1.f : 0.f;
+  PbBnD<CW> bd;
+  bd.init(a.mean, a.rstd, a.gamma, a.beta, a.coef, COUT, dact ? cc * CW : 0);
+  const float ghi = pb_gate_hi(a.act), glo = pb_gate_lo(a.act);
   const int xr = lane / XCH, xc = lane - (lane / XCH) * XCH;
   const bool xact = lane < 16 * XCH;
   // lane offset of chunk j inside a half (bytes): vd0 + j * RG rows; ROD_OOB: no row there
   const unsigned vd0 = dact ? (unsigned)((rg * COUT + cc * CW) * 2) : ROD_OOB;
-  auto vdj = [&](int j) -> unsigned {
-    if constexpr (JN * RG == 16) return vd0 + (unsigned)(j * RG * COUT * 2);
-    else return rg + RG * j < 16 ? vd0 + (unsigned)(j * RG * COUT * 2) : ROD_OOB;
-  };
+  auto vdj = [&](int j) -> unsigned { return pb_lane_off<JN, RG>(vd0, rg, j, COUT * 2); };
   const unsigned vx = xact ? (unsigned)((xr * CIN + xc * 8) * 2) : ROD_OOB;
   const long M = a.M;
-  auto rsrc_rows = [&](const void* base, long row0, int rowbytes) {   // rows [row0, min(row0 + 32, M))
-    const long rows = row0 < M ? (M - row0 < 32 ? M - row0 : 32) : 0;
-    return rod_rsrc((const char*)base + (row0 < M ? row0 : 0) * rowbytes, (unsigned)(rows * rowbytes));
-  };
+  auto rsrc_rows = [&](const void* base, long row0, int rowbytes) { return pb_rsrc_rows(base, M, row0, rowbytes); };
 
   f32x4 accw[NCO][NCI];
 #pragma unroll
@@ -467,14 +407,7 @@ __global__ void __launch_bounds__(256, CIN == 16 ? 3 : 1) pw_bwd_stream_kernel(P
           VT yj4;
           if constexpr (RC) yj4 = *(const VT*)dp;
           else yj4 = yv[j];
-          typename PbsVec<CW>::T o;
-#pragma unroll
-          for (int e = 0; e < CW; ++e) {
-            const float yj = (float)yj4[e];
-            const float z = fmaf(yj, sc[e], sh[e]);
-            const float gj = (float)dzv[j][e] * (z > 0.f ? (z < ghi ? 1.f : 0.f) : glo);
-            o[e] = (bf16_t)bn_bwd_apply1<bf16_t>(ca[e], gj, k1[e], k0[e], 0.f, yj);
-          }
+          const VT o = bd.dy(PbGate{ghi, glo}, dzv[j], yj4);
           dzv[j] = buf_ld<VT>(ndz, vdj(j), nso);
           if constexpr (!RC) yv[j] = buf_ld<VT>(ny, vdj(j), nso);
           if (rok) *(VT*)dp = o;
@@ -486,45 +419,19 @@ __global__ void __launch_bounds__(256, CIN == 16 ? 3 : 1) pw_bwd_stream_kernel(P
         bf16x8 v = xv;
         if constexpr (PRO) {
           const bool rok = row0 + h * 16 + xr < M;   // rows past M stay 0 (not act(shift))
-          const f32x4 s0 = *(const f32x4*)(xtab + xc * 8), s1 = *(const f32x4*)(xtab + xc * 8 + 4);
-          const f32x4 h0 = *(const f32x4*)(xtab + CIN + xc * 8), h1 = *(const f32x4*)(xtab + CIN + xc * 8 + 4);
-          if constexpr (XL) {   // linear input BatchNorm: packed pairs
-            const u32x4_t u = __builtin_bit_cast(u32x4_t, v);
-            u32x4_t o;
-#pragma unroll
-            for (int h2 = 0; h2 < 4; ++h2) {
-              const f32x4& sc4 = h2 < 2 ? s0 : s1;
-              const f32x4& sh4 = h2 < 2 ? h0 : h1;
-              const int b = (h2 & 1) * 2;
-              const pb_f2 z2 = __builtin_elementwise_fma(pb_unpack(u[h2]), pb_f2{sc4[b], sc4[b + 1]},
-                                                         pb_f2{sh4[b], sh4[b + 1]});
-              o[h2] = rok ? pb_round(z2) : 0u;
-            }
-            v = __builtin_bit_cast(bf16x8, o);
-          } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              v[e] = rok ? (bf16_t)act_fwd(fmaf((float)v[e], s0[e], h0[e]), a.xact) : (bf16_t)0.f;
-              v[4 + e] = rok ? (bf16_t)act_fwd(fmaf((float)v[4 + e], s1[e], h1[e]), a.xact) : (bf16_t)0.f;
-            }
-          }
+          float xsc[8], xsh[8];
+          pb_ld8(xtab + xc * 8, xsc);
+          pb_ld8(xtab + CIN + xc * 8, xsh);
+          if constexpr (XL) v = pb_xpro_linear(v, xsc, xsh, rok);   // linear input BatchNorm: packed pairs
+          else v = pb_xpro(v, xsc, xsh, a.xact, rok);
         }
         xv = buf_ld<bf16x8>(rsrc_rows(a.x, rown, CIN * 2), vx, (unsigned)((1 - h) * 16 * CIN * 2));
         if (xact) *(bf16x8*)(Xs + (h * 16 + xr) * LDX + xc * 8) = v;
       }
       __builtin_amdgcn_wave_barrier();
       if constexpr (RC) {
-        // y^T tile by tile: A = W rows (16 channels x k), B = this half's x rows (k x 16 rows);
-        // lane (g, li) gets channels 16ct + 4g .. +3 of row li -> one 8-byte LDS write per tile
-        const bf16x8 zero8 = {};
-        const bf16x8 fb = 8 * g < CIN ? *(const bf16x8*)(Xs + (h * 16 + li) * LDX + 8 * g) : zero8;
-#pragma unroll
-        for (int ct = 0; ct < NCO; ++ct) {
-          const bf16x8 fw = 8 * g < CIN ? *(const bf16x8*)(Wf + (ct * 16 + li) * G::LDW + 8 * g) : zero8;
-          const f32x4 yt = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw, fb, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-          const bf16x4 yb = {(bf16_t)yt[0], (bf16_t)yt[1], (bf16_t)yt[2], (bf16_t)yt[3]};
-          *(bf16x4*)(Ds + (h * 16 + li) * LDD + ct * 16 + 4 * g) = yb;
-        }
+        // y^T of this half from its x rows and the forward weights, into the half's dy rows
+        pb_rc_y_half<NCO, CIN>(Xs + h * 16 * LDX, LDX, Wf, G::LDW, Ds + h * 16 * LDD, LDD, lane);
         __builtin_amdgcn_wave_barrier();
         dy_rows();
         __builtin_amdgcn_wave_barrier();
@@ -532,17 +439,7 @@ __global__ void __launch_bounds__(256, CIN == 16 ? 3 : 1) pw_bwd_stream_kernel(P
       if constexpr (DX) {
         // ---- dx = dy . W for the 16 rows of this half -> Cx -> 16-byte row segments ---------
         f32x4 accx[NCI];
-#pragma unroll
-        for (int j = 0; j < NCI; ++j) accx[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < KT; ++s) {
-          const bf16x8 fa = *(const bf16x8*)(Ds + (h * 16 + li) * LDD + s * 32 + 8 * g);
-#pragma unroll
-          for (int j = 0; j < NCI; ++j) {
-            const bf16x8 fb = *(const bf16x8*)(Ws + (j * 16 + li) * LDD + s * 32 + 8 * g);
-            accx[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb, accx[j], 0, 0, 0);
-          }
-        }
+        pb_dx_half<KT, NCI>(Ds + h * 16 * LDD, Ws, LDD, lane, accx);
 #pragma unroll
         for (int j = 0; j < NCI; ++j) {
           const int col = j * 16 + li;
@@ -557,21 +454,13 @@ __global__ void __launch_bounds__(256, CIN == 16 ? 3 : 1) pw_bwd_stream_kernel(P
         buf_st(ov, rdx, vx, (unsigned)(h * 16 * CIN * 2));
         if constexpr (XG) {
           if (xact && row0 + h * 16 + xr < M) {
-            if constexpr (XL) {   // linear input BatchNorm (the project's): g = dx
+            // the constants are read from the LDS table per element, not held in registers
 #pragma unroll
-              for (int e = 0; e < 8; ++e) {
-                const float g = (float)ov[e];
-                xsg[e] += g;
-                xsgx[e] = fmaf(g, (float)xcur[e] - xtab[2 * CIN + xc * 8 + e], xsgx[e]);
-              }
-            } else {
-#pragma unroll
-              for (int e = 0; e < 8; ++e) {
-                const float xe = (float)xcur[e];
-                const float g = (float)ov[e] * act_grad(fmaf(xe, xtab[xc * 8 + e], xtab[CIN + xc * 8 + e]), a.xact);
-                xsg[e] += g;
-                xsgx[e] = fmaf(g, xe - xtab[2 * CIN + xc * 8 + e], xsgx[e]);
-              }
+            for (int e = 0; e < 8; ++e) {
+              const float mu = xtab[2 * CIN + xc * 8 + e];
+              if constexpr (XL) pb_xsum_linear((float)ov[e], (float)xcur[e], mu, xsg[e], xsgx[e]);   // the project's: g = dx
+              else gred_acc((float)ov[e], (float)xcur[e], xtab[xc * 8 + e], xtab[CIN + xc * 8 + e], mu, 1.f, a.xact,
+                            xsg[e], xsgx[e]);
             }
           }
         }
@@ -579,40 +468,14 @@ __global__ void __launch_bounds__(256, CIN == 16 ? 3 : 1) pw_bwd_stream_kernel(P
       }
     }
     // ---- dW += dy^T . x over the tile's 32 rows ---------------------------------------------
-#pragma unroll
-    for (int ct = 0; ct < NCO; ++ct) {
-      const bf16_t* pd = Ds + (8 * g + q) * LDD + ct * 16 + 4 * p;
-      const bf16x4 lo = pb_tr_read(pd), hi = pb_tr_read(pd + 4 * LDD);
-      const bf16x8 fa = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-#pragma unroll
-      for (int it = 0; it < NCI; ++it) {
-        const bf16_t* px = Xs + (8 * g + q) * LDX + it * 16 + 4 * p;
-        const bf16x4 l2 = pb_tr_read(px), h2 = pb_tr_read(px + 4 * LDX);
-        const bf16x8 fb = {l2[0], l2[1], l2[2], l2[3], h2[0], h2[1], h2[2], h2[3]};
-        accw[ct][it] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb, accw[ct][it], 0, 0, 0);
-      }
-    }
+    pb_dw_tiles<NCO, NCI>(Ds, LDD, Xs, LDX, lane, accw);
     __builtin_amdgcn_wave_barrier();   // the next tile's dy / x writes stay after these reads
   }
   // ---- the block's dW: the four waves add in wave order -> part blockIdx.x -----------------
   float* red = (float*)(smem + (size_t)(G::WS + G::XT) * 2);   // [COUT][NCI*16]
   constexpr int LR = NCI * 16;
   __syncthreads();
-#pragma unroll 1
-  for (int w = 0; w < 4; ++w) {
-    if (wave == w) {
-#pragma unroll
-      for (int ct = 0; ct < NCO; ++ct)
-#pragma unroll
-        for (int it = 0; it < NCI; ++it)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            float* d = red + (ct * 16 + 4 * g + r) * LR + it * 16 + li;
-            *d = w == 0 ? accw[ct][it][r] : *d + accw[ct][it][r];
-          }
-    }
-    __syncthreads();
-  }
+  pb_dw_wave_sum<NCO, NCI>(red, LR, wave, lane, accw);
   float* pw = a.partw + (long)blockIdx.x * COUT * CIN;
   for (int i = tid; i < COUT * CIN; i += 256) {
     const int co = i / CIN, ci = i - co * CIN;
@@ -620,21 +483,12 @@ __global__ void __launch_bounds__(256, CIN == 16 ? 3 : 1) pw_bwd_stream_kernel(P
   }
   if constexpr (XG) {   // waves, then the 16 row lanes of each chunk, added in a fixed order
     float* gbuf = red + COUT * LR;                                // [4][16][2][CIN]
-    if (xact) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        gbuf[((wave * 16 + xr) * 2 + 0) * CIN + xc * 8 + e] = xsg[e];
-        gbuf[((wave * 16 + xr) * 2 + 1) * CIN + xc * 8 + e] = xsgx[e];
-      }
-    }
+    if (xact) pb_xsum_stage(gbuf, 16, CIN, wave, xr, xc * 8, xsg, xsgx);
     __syncthreads();
     float* xp = xparts + (long)blockIdx.x * 2 * CIN;
     for (int i = tid; i < 2 * CIN; i += 256) {
       const int k = i / CIN, c = i - k * CIN;
-      float sum = 0.f;
-      for (int w = 0; w < 4; ++w)
-        for (int r = 0; r < 16; ++r) sum += gbuf[((w * 16 + r) * 2 + k) * CIN + c];
-      xp[i] = k ? sum * a.xrstd[c] : sum;
+      xp[i] = pb_xsum_col(gbuf, 16, CIN, k, c, a.xrstd[c]);
     }
   }
 }
@@ -695,32 +549,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) p
   bf16_t* Ds = Ws + G::WS + wave * G::WREG;                     // [32][LDD]  dy of the tile
   bf16_t* Xs = Ds + 32 * LDD;                                   // [32][LDX]  x_p of the tile
   bf16_t* Cx = Xs + 32 * LDX;                                   // [16][LDX]  dx staging
-  for (int i = tid; i < (G::WS + 4 * G::WREG) / 8; i += 256) {
-    bf16x8 z;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) z[j] = (bf16_t)0.f;
-    ((bf16x8*)smem)[i] = z;
-  }
+  pb_lds_zero(smem, (G::WS + 4 * G::WREG) / 8, tid);
   __syncthreads();
-  for (int i = tid; i < NW * (COUT / 8); i += 256) {
-    const int c = i / (COUT / 8), c8 = i - c * (COUT / 8);
-    *(bf16x8*)(Ws + c * LDD + c8 * 8) = *(const bf16x8*)(a.wt1 + (long)(n0 + c) * COUT + c8 * 8);
-  }
+  pb_load_wt1(Ws, LDD, a.wt1 + (long)n0 * COUT, NW, COUT, tid);
   __syncthreads();
 
   // ---- lane constants: dy chunk (4 channels of Cout) and x chunk (8 columns of the group) ----
   const int rg = lane / CCH, cc = lane - (lane / CCH) * CCH;
   const bool dact = rg < RG;
-  float sc[4], sh[4], ca[4], k1[4], k0[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int c = (dact ? cc * 4 : 0) + e;
-    bn_affine(a.mean, a.rstd, a.gamma, a.beta, c, sc[e], sh[e]);
-    ca[e] = a.coef[c];
-    bn_bwd_k_fold(ca[e], a.mean[c], a.rstd[c], a.coef[COUT + c], a.coef[2 * COUT + c], k1[e], k0[e]);
-  }
-  const float ghi = a.act == ROD_ACT_RELU6 ? 6.f : INFINITY;
-  const float glo = a.act == ROD_ACT_LEAKY ? 0.2f : a.act == ROD_ACT_NONE ? 1.f : 0.f;
+  PbBnD<4> bd;
+  bd.init(a.mean, a.rstd, a.gamma, a.beta, a.coef, COUT, dact ? cc * 4 : 0);
+  const float ghi = pb_gate_hi(a.act), glo = pb_gate_lo(a.act);
   const int rx = lane / XCH, xc = lane - (lane / XCH) * XCH;
   const bool xact = rx < RGX;
   // sgx sums g*(x - mean); the rstd factor is applied once per column at the end
@@ -737,9 +576,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) p
   if constexpr (FAST) {
 #pragma unroll
     for (int h2 = 0; h2 < 2; ++h2) {
-      ca2[h2] = pb_f2{ca[2 * h2], ca[2 * h2 + 1]};
-      k12[h2] = pb_f2{k1[2 * h2], k1[2 * h2 + 1]};
-      k02[h2] = pb_f2{k0[2 * h2], k0[2 * h2 + 1]};
+      ca2[h2] = pb_f2{bd.ca[2 * h2], bd.ca[2 * h2 + 1]};
+      k12[h2] = pb_f2{bd.k1[2 * h2], bd.k1[2 * h2 + 1]};
+      k02[h2] = pb_f2{bd.k0[2 * h2], bd.k0[2 * h2 + 1]};
     }
 #pragma unroll
     for (int h2 = 0; h2 < 4; ++h2) {
@@ -750,25 +589,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) p
   }
   pb_f2 sg2[4] = {}, sgx2[4] = {};
   const unsigned vd0 = dact ? (unsigned)((rg * COUT + cc * 4) * 2) : ROD_OOB;
-  auto vdj = [&](int j) -> unsigned {
-    if constexpr (JN * RG == 16) return vd0 + (unsigned)(j * RG * COUT * 2);
-    else return rg + RG * j < 16 ? vd0 + (unsigned)(j * RG * COUT * 2) : ROD_OOB;
-  };
+  auto vdj = [&](int j) -> unsigned { return pb_lane_off<JN, RG>(vd0, rg, j, COUT * 2); };
   const unsigned vx0 = xact ? (unsigned)((rx * Cin + xc * 8) * 2) : ROD_OOB;
-  auto vxj = [&](int j) -> unsigned {
-    if constexpr (JX * RGX == 16) return vx0 + (unsigned)(j * RGX * Cin * 2);
-    else return rx + RGX * j < 16 ? vx0 + (unsigned)(j * RGX * Cin * 2) : ROD_OOB;
-  };
+  auto vxj = [&](int j) -> unsigned { return pb_lane_off<JX, RGX>(vx0, rx, j, Cin * 2); };
   const long M = a.M;
-  auto rows_of = [&](long row0) -> long { return row0 < M ? (M - row0 < 32 ? M - row0 : 32) : 0; };
-  auto rsrc_d = [&](const void* base, long row0) {   // dz / y rows [row0, +32) of Cout channels
-    return rod_rsrc((const char*)base + (row0 < M ? row0 : 0) * COUT * 2, (unsigned)(rows_of(row0) * COUT * 2));
-  };
-  auto rsrc_x = [&](const void* base, long row0) {   // x / dx rows of this group's columns
-    const long r = rows_of(row0);
-    return rod_rsrc((const char*)base + ((row0 < M ? row0 : 0) * Cin + n0) * 2,
-                    r > 0 ? (unsigned)(((r - 1) * Cin + NW) * 2) : 0u);
-  };
+  // dz / y rows [row0, +32) of Cout channels; x / dx rows of this group's columns
+  auto rsrc_d = [&](const void* base, long row0) { return pb_rsrc_rows(base, M, row0, COUT * 2); };
+  auto rsrc_x = [&](const void* base, long row0) { return pb_rsrc_cols(base, M, row0, Cin, n0, NW); };
 
   f32x4 accw[NCO][NWT];
 #pragma unroll
@@ -820,19 +647,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) p
             u32x2_t ou;
 #pragma unroll
             for (int h2 = 0; h2 < 2; ++h2) {
-              const pb_f2 y2 = pb_unpack(yu[h2]), d2 = pb_unpack(du[h2]);
-              const pb_f2 t2 = __builtin_elementwise_fma(k12[h2], y2, k02[h2]);
-              ou[h2] = rok ? pb_round(__builtin_elementwise_fma(ca2[h2], d2, t2)) : 0u;
+              const pb_f2 dy2 = pb_dy_pair_linear(ca2[h2], k12[h2], k02[h2], pb_unpack(du[h2]), pb_unpack(yu[h2]));
+              ou[h2] = rok ? pb_round(dy2) : 0u;
             }
             o = __builtin_bit_cast(bf16x4, ou);
           } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float yj = (float)yv[j][e];
-              const float z = fmaf(yj, sc[e], sh[e]);
-              const float gj = (float)dzv[j][e] * (z > 0.f ? (z < ghi ? 1.f : 0.f) : glo);
-              o[e] = rok ? (bf16_t)bn_bwd_apply1<bf16_t>(ca[e], gj, k1[e], k0[e], 0.f, yj) : (bf16_t)0.f;
-            }
+            const bf16x4 zero4 = {};
+            o = rok ? bd.dy(PbGate{ghi, glo}, dzv[j], yv[j]) : zero4;
           }
           dzv[j] = buf_ld<bf16x4>(ndz, vdj(j), nso);
           yv[j] = buf_ld<bf16x4>(ny, vdj(j), nso);
@@ -846,38 +667,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) p
         const int r = rx + RGX * j;
         const bool rok = row0 + h * 16 + r < M;
         bf16x8 v;
-        if constexpr (FAST) {   // ReLU6 input BatchNorm
-          const u32x4_t xu = __builtin_bit_cast(u32x4_t, xv[j]);
-          u32x4_t vu;
-#pragma unroll
-          for (int h2 = 0; h2 < 4; ++h2) {
-            const pb_f2 z2 = __builtin_elementwise_fma(pb_unpack(xu[h2]), xsc2[h2], xsh2[h2]);
-            const pb_f2 t2 = {act_t<ROD_ACT_RELU6>(z2.x), act_t<ROD_ACT_RELU6>(z2.y)};
-            vu[h2] = rok ? pb_round(t2) : 0u;
-          }
-          v = __builtin_bit_cast(bf16x8, vu);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e)
-            v[e] = rok ? (bf16_t)act_fwd(fmaf((float)xv[j][e], xsc[e], xsh[e]), a.xact) : (bf16_t)0.f;
-        }
+        if constexpr (FAST) v = pb_xpro_relu6(xv[j], xsc2, xsh2, rok);   // ReLU6 input BatchNorm, packed
+        else v = pb_xpro(xv[j], xsc, xsh, a.xact, rok);
         if (xact && (JX * RGX == 16 || r < 16)) *(bf16x8*)(Xs + (h * 16 + r) * LDX + xc * 8) = v;
       }
       __builtin_amdgcn_wave_barrier();
       // ---- dx = dy . W for the half -> Cx; written by the x lanes with the BN_x sums ------------
       {
         f32x4 accx[NWT];
-#pragma unroll
-        for (int j = 0; j < NWT; ++j) accx[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < KT; ++s) {
-          const bf16x8 fa = *(const bf16x8*)(Ds + (h * 16 + li) * LDD + s * 32 + 8 * g);
-#pragma unroll
-          for (int j = 0; j < NWT; ++j) {
-            const bf16x8 fb = *(const bf16x8*)(Ws + (j * 16 + li) * LDD + s * 32 + 8 * g);
-            accx[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb, accx[j], 0, 0, 0);
-          }
-        }
+        pb_dx_half<KT, NWT>(Ds + h * 16 * LDD, Ws, LDD, lane, accx);
 #pragma unroll
         for (int j = 0; j < NWT; ++j)
 #pragma unroll
@@ -892,17 +690,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) p
           const bf16x8 dv = *(const bf16x8*)(Cx + (r < 16 ? r : 0) * LDX + xc * 8);
           buf_st(dv, rdx, vxj(j), so);
           if (rok) {
-            if constexpr (FAST) {   // g = dx where 0 < z < 6; sums of g and g*(x - mean), in pairs
-              const u32x4_t du = __builtin_bit_cast(u32x4_t, dv), xu = __builtin_bit_cast(u32x4_t, xv[j]);
-#pragma unroll
-              for (int h2 = 0; h2 < 4; ++h2) {
-                const pb_f2 x2 = pb_unpack(xu[h2]), d2 = pb_unpack(du[h2]);
-                const pb_f2 z2 = __builtin_elementwise_fma(x2, xsc2[h2], xsh2[h2]);
-                const pb_f2 g2 = {pb_relu6_open(z2.x) ? d2.x : 0.f, pb_relu6_open(z2.y) ? d2.y : 0.f};
-                sg2[h2] += g2;
-                sgx2[h2] = __builtin_elementwise_fma(g2, x2 - xmu2[h2], sgx2[h2]);
-              }
-            } else {
+            // FAST: g = dx where 0 < z < 6; sums of g and g*(x - mean), in pairs
+            if constexpr (FAST) pb_xsum_relu6(dv, xv[j], xsc2, xsh2, xmu2, sg2, sgx2);
+            else {
 #pragma unroll
               for (int e = 0; e < 8; ++e)
                 gred_acc((float)dv[e], (float)xv[j][e], xsc[e], xsh[e], xmu[e], 1.f, a.xact, sg[e], sgx[e]);
@@ -915,19 +705,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) p
       for (int j = 0; j < JX; ++j) xv[j] = xn[j];
     }
     // ---- dW += dy^T . x_p over the tile's 32 rows -------------------------------------------
-#pragma unroll
-    for (int ct = 0; ct < NCO; ++ct) {
-      const bf16_t* pd = Ds + (8 * g + q) * LDD + ct * 16 + 4 * p;
-      const bf16x4 lo = pb_tr_read(pd), hi = pb_tr_read(pd + 4 * LDD);
-      const bf16x8 fa = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-#pragma unroll
-      for (int it = 0; it < NWT; ++it) {
-        const bf16_t* px = Xs + (8 * g + q) * LDX + it * 16 + 4 * p;
-        const bf16x4 l2 = pb_tr_read(px), h2 = pb_tr_read(px + 4 * LDX);
-        const bf16x8 fb = {l2[0], l2[1], l2[2], l2[3], h2[0], h2[1], h2[2], h2[3]};
-        accw[ct][it] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb, accw[ct][it], 0, 0, 0);
-      }
-    }
+    pb_dw_tiles<NCO, NWT>(Ds, LDD, Xs, LDX, lane, accw);
     __builtin_amdgcn_wave_barrier();
   }
   // ---- end: dW (waves in order) and the BN_x sums (waves, then row groups, in order) -------
@@ -941,28 +719,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) p
       sgx[e] = sgx2[e >> 1][e & 1];
     }
   }
-  if (xact) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      gbuf[((wave * RGX + rx) * 2 + 0) * NW + xc * 8 + e] = sg[e];
-      gbuf[((wave * RGX + rx) * 2 + 1) * NW + xc * 8 + e] = sgx[e];
-    }
-  }
-#pragma unroll 1
-  for (int w = 0; w < 4; ++w) {
-    if (wave == w) {
-#pragma unroll
-      for (int ct = 0; ct < NCO; ++ct)
-#pragma unroll
-        for (int it = 0; it < NWT; ++it)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            float* d = red + (ct * 16 + 4 * g + r) * NW + it * 16 + li;
-            *d = w == 0 ? accw[ct][it][r] : *d + accw[ct][it][r];
-          }
-    }
-    __syncthreads();
-  }
+  if (xact) pb_xsum_stage(gbuf, RGX, NW, wave, rx, xc * 8, sg, sgx);
+  pb_dw_wave_sum<NCO, NWT>(red, NW, wave, lane, accw);
   float* pw = a.partw + (long)blockIdx.x * COUT * Cin;
   for (int i = tid; i < COUT * NW; i += 256) {
     const int co = i / NW, c = i - co * NW;
@@ -971,10 +729,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) p
   float* xp = xparts + (long)blockIdx.x * 2 * Cin;
   for (int i = tid; i < 2 * NW; i += 256) {
     const int k = i / NW, c = i - k * NW;
-    float s = 0.f;
-    for (int w = 0; w < 4; ++w)
-      for (int r = 0; r < RGX; ++r) s += gbuf[((w * RGX + r) * 2 + k) * NW + c];
-    xp[(long)k * Cin + n0 + c] = k ? s * a.xrstd[n0 + c] : s;
+    xp[(long)k * Cin + n0 + c] = pb_xsum_col(gbuf, RGX, NW, k, c, a.xrstd[n0 + c]);
   }
 }
 
@@ -1040,6 +795,36 @@ static PwBwdPlan pw_bwd_plan(long M, int Cin, int Cout, bool bias) {
   return p;
 }
 
+// the arguments every form takes; the launch-specific fields (partb / chunk / kd .. nxt of the
+// block kernel's plan, dyp, wt0) stay 0 / NULL and are set by name where a form uses them
+static PwBwdArgs pb_args(const void* dz, const void* y, const void* x, const void* wt1, void* dx, float* partw,
+                         const float* mean, const float* rstd, const float* gamma, const float* beta,
+                         const float* coef, int act, const float* xmean, const float* xrstd, const float* xgamma,
+                         const float* xbeta, int xact, long M, int Cin, int Cout) {
+  PwBwdArgs a{};
+  a.dz = (const bf16_t*)dz, a.y = (const bf16_t*)y, a.x = (const bf16_t*)x, a.wt1 = (const bf16_t*)wt1;
+  a.dx = (bf16_t*)dx, a.partw = partw;
+  a.mean = mean, a.rstd = rstd, a.gamma = gamma, a.beta = beta, a.coef = coef, a.act = act;
+  a.xmean = xmean, a.xrstd = xrstd, a.xgamma = xgamma, a.xbeta = xbeta, a.xact = xact;
+  a.M = M, a.Cin = Cin, a.Cout = Cout;
+  return a;
+}
+
+// the pointer checks of both run functions, in two steps so that each keeps its place among the
+// entry's own checks: `have` is the entry's list of required pointers
+static int pb_check_ptrs(const char* who, bool have, const void* wt0) {
+  ROD_CHECK_ARG(have, "%s: NULL argument", who);
+  ROD_CHECK_ARG((((uintptr_t)wt0) & 15) == 0, "%s_rc: wt0 must be 16-byte aligned", who);
+  return 0;
+}
+static int pb_check_align(const char* who, const void* dz, const void* y, const void* x, const void* wt1,
+                          const void* dx, const void* dyp) {
+  ROD_CHECK_ARG(((((uintptr_t)dz) | ((uintptr_t)y) | ((uintptr_t)x) | ((uintptr_t)wt1) | ((uintptr_t)dx) |
+                  ((uintptr_t)dyp)) & 15) == 0,
+                "%s: tensors must be 16-byte aligned", who);
+  return 0;
+}
+
 }  // namespace rod
 
 using namespace rod;
@@ -1066,23 +851,22 @@ static int pw_bwd_run(const void* dz, const void* y, const void* wt0, const floa
                       int dtype, void* stream) {
   ROD_CHECK_ARG(dtype == ROD_BF16, "rod_pw_bwd: bf16 only");
   ROD_CHECK_ARG(M > 0 && pw_bwd_ok(Cin, Cout), "rod_pw_bwd: unsupported shape M=%ld Cin=%d Cout=%d", M, Cin, Cout);
-  ROD_CHECK_ARG(dz && (y || wt0) && mean && rstd && coef && x && dw && workspace, "rod_pw_bwd: NULL argument");
+  if (const int e = pb_check_ptrs("rod_pw_bwd", dz && (y || wt0) && mean && rstd && coef && x && dw && workspace, wt0))
+    return e;
   ROD_CHECK_ARG(!wt0 || (!db && rod_pw_bwd_rc_supported(M, Cin, Cout, dtype)),
                 "rod_pw_bwd_rc: the recompute form takes the streaming shapes (16 -> 96, 24 -> 144) without bias");
-  ROD_CHECK_ARG((((uintptr_t)wt0) & 15) == 0, "rod_pw_bwd_rc: wt0 must be 16-byte aligned");
   ROD_CHECK_ARG(!dx || wt1, "rod_pw_bwd: dx needs wt1");
   ROD_CHECK_ARG(!xmean || xrstd, "rod_pw_bwd: bad input prologue");
-  ROD_CHECK_ARG(((((uintptr_t)dz) | ((uintptr_t)y) | ((uintptr_t)x) | ((uintptr_t)wt1) | ((uintptr_t)dx)) & 15) == 0,
-                "rod_pw_bwd: tensors must be 16-byte aligned");
+  if (const int e = pb_check_align("rod_pw_bwd", dz, y, x, wt1, dx, nullptr)) return e;
   const PwBwdPlan p = pw_bwd_plan(M, Cin, Cout, db != nullptr);
   ROD_CHECK_ARG(p.lds <= 160 * 1024, "rod_pw_bwd: LDS plan too large");
   hipStream_t s = ROD_STREAM(stream);
   float* partw = (float*)workspace;
   if (pw_bwd_stream_ok(Cin, Cout, db != nullptr)) {
     const int nblk = pw_bwd_stream_blocks(M);
-    PwBwdArgs a{(const bf16_t*)dz, (const bf16_t*)y, (const bf16_t*)x, (const bf16_t*)wt1, (bf16_t*)dx, partw, nullptr,
-                mean, rstd, gamma, beta, coef, xmean, xrstd, xgamma, xbeta, act, xact, M, 0, Cin, Cout, 0, 0, 0, 0,
-                nullptr, (const bf16_t*)wt0};
+    PwBwdArgs a = pb_args(dz, y, x, wt1, dx, partw, mean, rstd, gamma, beta, coef, act, xmean, xrstd, xgamma, xbeta,
+                          xact, M, Cin, Cout);
+    a.wt0 = (const bf16_t*)wt0;
     const long ntiles = cdivl(M, 32);
     // PR: input prologue, DXF: dx wanted, XL: the prologue without an activation (built for
     // either PR, selected only with it), RCF: y recomputed from wt0
@@ -1106,9 +890,9 @@ static int pw_bwd_run(const void* dz, const void* y, const void* wt0, const floa
     return check_launch("rod_pw_bwd");
   }
   float* partb = db ? partw + (size_t)p.nblk * Cout * Cin : nullptr;
-  PwBwdArgs a{(const bf16_t*)dz, (const bf16_t*)y, (const bf16_t*)x, (const bf16_t*)wt1, (bf16_t*)dx, partw, partb,
-              mean, rstd, gamma, beta, coef, xmean, xrstd, xgamma, xbeta, act, xact, M, p.chunk,
-              Cin, Cout, p.kd, p.nci, p.nco, p.nxt};
+  PwBwdArgs a = pb_args(dz, y, x, wt1, dx, partw, mean, rstd, gamma, beta, coef, act, xmean, xrstd, xgamma, xbeta, xact,
+                        M, Cin, Cout);
+  a.partb = partb, a.chunk = p.chunk, a.kd = p.kd, a.nci = p.nci, a.nco = p.nco, a.nxt = p.nxt;
   // p.nx is 2 / 4 / 8 / 12 A tiles and p.wt 4 / 6 / 8 / 16 weight tiles per wave (pw_bwd_plan)
   const bool hit = sel_int<2, 4, 8, 12>(p.nx, [&](auto NX) {
     return sel_int<4, 6, 8, 16>(p.wt, [&](auto WT) {
@@ -1167,22 +951,20 @@ static int pw_bwd_gred_run(const void* dz, const void* y, const float* mean, con
   ROD_CHECK_ARG(nw || sexp, "rod_pw_bwd_gred: unsupported shape M=%ld Cin=%d Cout=%d dtype=%d", M, Cin, Cout,
                 dtype);
   ROD_CHECK_ARG(!wt0 || sexp, "rod_pw_bwd_gred_rc: the recompute form takes the 16 -> 96 expand only");
-  ROD_CHECK_ARG(dz && (y || wt0) && mean && rstd && coef && x && xmean && xrstd && dw && xparts && workspace,
-                "rod_pw_bwd_gred: NULL argument");
-  ROD_CHECK_ARG((((uintptr_t)wt0) & 15) == 0, "rod_pw_bwd_gred_rc: wt0 must be 16-byte aligned");
+  if (const int e = pb_check_ptrs("rod_pw_bwd_gred", dz && (y || wt0) && mean && rstd && coef && x && xmean && xrstd &&
+                                  dw && xparts && workspace, wt0))
+    return e;
   ROD_CHECK_ARG((dx != nullptr) != (dyp != nullptr) && wt1,
                 "rod_pw_bwd_gred: wt1 and exactly one of dx / dyp required (the sums are over dx)");
-  ROD_CHECK_ARG(((((uintptr_t)dz) | ((uintptr_t)y) | ((uintptr_t)x) | ((uintptr_t)wt1) | ((uintptr_t)dx) |
-                  ((uintptr_t)dyp)) & 15) == 0,
-                "rod_pw_bwd_gred: tensors must be 16-byte aligned");
+  if (const int e = pb_check_align("rod_pw_bwd_gred", dz, y, x, wt1, dx, dyp)) return e;
   ROD_CHECK_ARG(M * Cin * 2 < (1L << 31) && M * Cout * 2 < (1L << 31), "rod_pw_bwd_gred: tensor over 2 GiB");
   hipStream_t s = ROD_STREAM(stream);
   float* partw = (float*)workspace;
   if (sexp) {   // an expand shape: the streaming kernel with the input BatchNorm's sums
     const int nb = pw_bwd_stream_blocks(M);
-    PwBwdArgs a{(const bf16_t*)dz, (const bf16_t*)y, (const bf16_t*)x, (const bf16_t*)wt1, (bf16_t*)dx, partw,
-                nullptr, mean, rstd, gamma, beta, coef, xmean, xrstd, xgamma, xbeta, act, xact, M, 0, Cin, Cout, 0, 0,
-                0, 0, nullptr, (const bf16_t*)wt0};
+    PwBwdArgs a = pb_args(dz, y, x, wt1, dx, partw, mean, rstd, gamma, beta, coef, act, xmean, xrstd, xgamma, xbeta,
+                          xact, M, Cin, Cout);
+    a.wt0 = (const bf16_t*)wt0;
     const long nt = cdivl(M, 32);
     // sexp: 16 -> 96 only (pw_bwd_xg_ok)
     sel_bool(xact == ROD_ACT_NONE, [&](auto XL) {
@@ -1195,9 +977,9 @@ static int pw_bwd_gred_run(const void* dz, const void* y, const float* mean, con
     return check_launch("rod_pw_bwd_gred");
   }
   const int nblk = pw_bwd_gred_rowblocks(M, Cin, nw);
-  PwBwdArgs a{(const bf16_t*)dz, (const bf16_t*)y, (const bf16_t*)x, (const bf16_t*)wt1, (bf16_t*)dx, partw, nullptr,
-              mean, rstd, gamma, beta, coef, xmean, xrstd, xgamma, xbeta, act, xact, M, 0, Cin, Cout, 0, 0, 0, 0,
-              (bf16_t*)dyp};
+  PwBwdArgs a = pb_args(dz, y, x, wt1, dx, partw, mean, rstd, gamma, beta, coef, act, xmean, xrstd, xgamma, xbeta, xact,
+                        M, Cin, Cout);
+  a.dyp = (bf16_t*)dyp;
   const long ntiles = cdivl(M, 32);
   const dim3 grid(nblk, Cin / nw);
   // the inverted-residual block's case takes the packed form; at 48 columns it measured slower

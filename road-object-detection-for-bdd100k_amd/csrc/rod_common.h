@@ -109,6 +109,15 @@ template <typename V> __device__ __forceinline__ void buf_st(const V& v, rsrc_t 
   __builtin_amdgcn_sched_barrier(0);
 }
 
+// Transposed LDS read (ds_read_b64_tr_b16): within each 16-lane group the lanes' 8-byte rows are
+// read as a 16 x 4 bf16 block and handed out transposed, so an MFMA operand whose k runs down the
+// LDS rows (the weight gradients' dy^T and x^T) needs no transposing store.  p is 8-byte aligned.
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ bf16x4 lds_tr_read(const bf16_t* p) {
+  s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
+  return __builtin_bit_cast(bf16x4, r);
+}
+
 // Correctly-rounded f32 transcendental functions (evaluated in f64 and
 // rounded once).  The oracle uses the same definition (np.float64 then cast),
 // so integer decisions downstream of exp/log are reproducible bit for bit.

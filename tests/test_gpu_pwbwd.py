@@ -6,11 +6,17 @@ backward (TF FusedBatchNormGrad + Conv2DBackpropInput / Filter semantics).
 dy is formed with rod_bn_bwd_apply's arithmetic and rounded the same way, and dx = dy.W runs
 the same MFMA k order as the unfused backward-data GEMM, so dx is bit-identical; dw / db sum
 the rows in a different order (fp32 partials, f64 slab sum): within 1e-5 normwise."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 from rod import ops
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from pwbwd_ref import nerr as _nerr, unfused_chain  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 bf16 = torch.bfloat16
@@ -27,11 +33,6 @@ SHAPES = [  # (M, Cin, Cout, act, pro_x, bias)
     (130, 96, 128, ops.ROD_ACT_LEAKY, True, True),
     (2049, 128, 24, ops.ROD_ACT_LEAKY, True, True),           # head 128->24
 ]
-
-
-def _nerr(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
 
 
 @pytest.mark.parametrize('M,Cin,Cout,act,prox,bias', SHAPES)
@@ -54,17 +55,7 @@ def test_pw_bwd_matches_unfused_chain(dev, M, Cin, Cout, act, prox, bias):
                 ops.ROD_ACT_RELU6)
     coef = ops.bn_bwd_reduce(dz, y, mean, rstd, gamma, beta, act, False, False)
     wt1 = ops._prep(w, 1, bf16, Cout, Cin, 1)
-    # unfused
-    dy = torch.empty_like(y)
-    ops._abi.call('rod_bn_bwd_apply', dz, y, mean, rstd, gamma, beta, coef, dy, M, Cout, act, ops.dtcode(y),
-                  ops.stream())
-    dx_ref = torch.empty_like(x)
-    ops.conv_fwd_raw(dy, wt1, None, dx_ref, 1, 1, M, Cout, Cin, 1)
-    dw_ref = torch.empty(Cout, Cin, device=dev)
-    db_ref = torch.empty(Cout, device=dev) if bias else None
-    wsz = ops._abi.query('rod_conv_wgrad_workspace', 1, 1, M, Cin, Cout, 1)
-    ops._abi.call('rod_conv_wgrad', x, *ops._pro_args(xpro), dy, dw_ref, db_ref, ops.workspace(wsz, dev), 1, 1, M, Cin,
-                  Cout, 1, 0, 0, ops.dtcode(x), ops.stream())
+    _, dx_ref, dw_ref, db_ref = unfused_chain(dz, y, mean, rstd, gamma, beta, act, coef, x, xpro, wt1, bias)
     # fused
     dw = torch.full((Cout, Cin), float('nan'), device=dev)
     db = torch.full((Cout,), float('nan'), device=dev) if bias else None
@@ -195,15 +186,7 @@ def test_pw_bwd_gred_matches_unfused_chain(dev, M, Cin, Cout, act):
             ops.ROD_ACT_RELU6)
     coef = ops.bn_bwd_reduce(dz, y, mean, rstd, gamma, beta, act, False, False)
     wt1 = ops._prep(w, 1, bf16, Cout, Cin, 1)
-    dy = torch.empty_like(y)
-    ops._abi.call('rod_bn_bwd_apply', dz, y, mean, rstd, gamma, beta, coef, dy, M, Cout, act, ops.dtcode(y),
-                  ops.stream())
-    dx_ref = torch.empty_like(x)
-    ops.conv_fwd_raw(dy, wt1, None, dx_ref, 1, 1, M, Cout, Cin, 1)
-    dw_ref = torch.empty(Cout, Cin, device=dev)
-    wsz = ops._abi.query('rod_conv_wgrad_workspace', 1, 1, M, Cin, Cout, 1)
-    ops._abi.call('rod_conv_wgrad', x, *ops._pro_args(xpro), dy, dw_ref, None, ops.workspace(wsz, dev), 1, 1, M, Cin,
-                  Cout, 1, 0, 0, ops.dtcode(x), ops.stream())
+    _, dx_ref, dw_ref, _ = unfused_chain(dz, y, mean, rstd, gamma, beta, act, coef, x, xpro, wt1)
     dw = torch.full((Cout, Cin), float('nan'), device=dev)
     dx, xparts = ops.pw_bwd_gred(dz, y, mean, rstd, gamma, beta, act, coef, x, xpro, wt1, dw)
     assert xparts.shape == (nparts, 2, Cin)

@@ -45,7 +45,7 @@ def test_stem_full_width(dev):
     torch.testing.assert_close(z1.float(), z2.float(), rtol=1e-2, atol=2e-2)
 
 
-@pytest.mark.parametrize('N,H,W', [(2, 37, 300), (1, 720, 1280)])
+@pytest.mark.parametrize('N,H,W', [(2, 37, 300), (1, 720, 1280), (1, 3, 65)])
 def test_stem_wgrad_bn_matches_apply_then_wgrad(dev, N, H, W):
     """rod_stem_wgrad_bn (dy formed from the stem BatchNorm's (dz, y) in the weight gradient's
     loader) against rod_bn_bwd_apply -> rod_conv_wgrad: the same dy rounding and MFMA order, so
